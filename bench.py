@@ -16,12 +16,20 @@ when timing starts.
 Multi-GPU (one process per GPU, aircraft are independent, NO data-path collective). For --gpus > 1 the default is `--scaling strong`:
 BASELINE.json's metric is the whole node at N = 1 M, i.e. the SAME 1 048 576 aircraft cut into contiguous shards
 (flightbatch.sharding.shard_range), 131 072 per GPU at N = 8, and `value` is the whole job's rate on THAT configuration. The weak figure —
-every rank stepping its own 1 048 576 aircraft (configs[2] per GPU, rank r on lattice(r)) — is measured in the same run and attached as
-"weak_scaling" (`--scaling weak` makes it the headline instead). One RCCL all-gather of the final states collects the
+every rank stepping its own 1 048 576 aircraft (configs[2] per GPU, rank r on lattice(r)) — is measured in the same run with --full and
+attached as "weak_scaling" (`--scaling weak` makes it the headline instead). One RCCL all-gather of the final states collects the
 trajectory endpoint after the timed region (gather_ms, not part of `value`). At --gpus 1 the two coincide.
 
-On one GPU the line also carries, under "extra", one GPU's share of configs[3] (524 288 Cessna172Xv2 with the autopilot at
-Δt = 0.02) and configs[4] (mixed fp32 fleet, 50 % Cessna172Sv0 / 50 % Robot2D), each with its own timing and parity sample.
+A plain run does only what the headline needs: set-up (trim and upload), `--warmup` launches, the `--steps` timed launches, the
+validity checks on every aircraft, and the result line. `--full` adds everything else the benchmark measures: the CPU baseline and
+the parity sample against the oracle (`cpu_baseline`, `rel_err_vs_cpu`), at N > 1 the other scaling mode, and on one GPU, under
+"extra", one GPU's share of configs[3] (524 288 Cessna172Xv2 with the autopilot at Δt = 0.02) and configs[4] (mixed fp32 fleet,
+50 % Cessna172Sv0 / 50 % Robot2D), each with its own timing and parity sample (--no-cpu-baseline / --no-extra leave parts of it out).
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, for a fixed seeded sample of OUTPUT_SAMPLE aircraft
+(rank 0's shard at N > 1): DIR/x.npy [FB_NX, m] (state), s.npy [FB_NS, m] (discrete state), status.npy [m] and index.npy [m]
+(the aircraft's place in the batch), all float64 (the stepping launches evaluate no output record: there is no y to write). The inputs depend on the
+arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +53,8 @@ HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6      # MI355X vector fp64 peak (spec): 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
 PROFILE_COUNTERS = "r06_counters.json"
 PROFILE_COUNTERS_X2 = "r06_x2_counters.json"   # the same for the Cessna172Xv2 airborne stepper (tools/collect_profile_x2.sh)   # rocprofv3 PMC summary of the CURRENT airborne stepper (tools/collect_profile.sh)
+OUTPUT_SAMPLE = 65536    # aircraft in --dump-outputs: (27 + 2 + 2) rows x 8 B x 65 536 = 16 MB
+OUTPUT_SEED = 1172
 
 
 def lattice(seed_offset: int = 0, n: int = N_TOTAL):
@@ -70,6 +80,24 @@ def stratified_sample(cell: np.ndarray, per_cell: int = 4, seed: int = 2) -> np.
     bounds = np.flatnonzero(np.diff(cell[order])) + 1
     groups = np.split(order, bounds)
     return np.sort(np.concatenate([rng.choice(g, size=min(per_cell, g.size), replace=False) for g in groups]))
+
+
+def output_sample(n: int) -> np.ndarray:
+    """the aircraft --dump-outputs writes: OUTPUT_SAMPLE indices of a batch of n, drawn once from a fixed seed, ascending"""
+    if n <= OUTPUT_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(OUTPUT_SEED).choice(n, size=OUTPUT_SAMPLE, replace=False))
+
+
+def sample_outputs(x, s, st, sel) -> dict:
+    """what a caller of the timed path receives (mdl.x, mdl.s, the status word), at the aircraft `sel`, as float64"""
+    return {"x": x[:, sel], "s": s[:, sel].astype(np.float64), "status": st[sel].astype(np.float64), "index": sel.astype(np.float64)}
+
+
+def write_outputs(path: str, outputs: dict) -> None:
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def usable_cores() -> int:
@@ -212,9 +240,9 @@ def warm_until_stable(fb, C, w, launch, tol=0.01, cap=30, at_least=3):
     return seen
 
 
-def time_c172s0(fb, torch, dist, C, EAS, h, psi, args, local_rank, world):
+def time_c172s0(fb, torch, dist, C, EAS, h, psi, args, local_rank, world, dump=False):
     """trim + warm-up + the timed region for one shard of the Cessna172Sv0 batch. Returns a dict of measurements (and the
-    initial condition on the host, for the CPU legs)."""
+    initial condition on the host, for the CPU legs); with `dump`, also the sampled outputs of the last timed step."""
     n = len(EAS)
     w = fb.BatchedWorld(n, device=local_rank, dtype=args.dtype)
     # the state lives in a torch tensor so that RCCL can gather it without a host round trip
@@ -253,6 +281,8 @@ def time_c172s0(fb, torch, dist, C, EAS, h, psi, args, local_rank, world):
     # full-size invariants over ALL aircraft of the shard
     st = w.status
     xf = w.x
+    if dump:
+        out["outputs"] = sample_outputs(xf, w.s, st, output_sample(n))
     out["status_bad"] = int((st != 0).sum())
     out["fuel_not_decreasing"] = int((xf[8] >= fuel0).sum())
     qtol = 1.1e-8 if args.dtype == "f64" else 5e-7    # f_step! renormalises beyond 1e-8 (kinematics.jl:114-118); the fp32 stepper holds q_wb to fp32 rounding
@@ -547,11 +577,16 @@ def main():
     ap.add_argument("--x2-inner", type=int, default=50, help="RK4 steps per launch of the Cessna172Xv2 stepper (control laws run inside the launch)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default=None,
                     help="N > 1: strong (default) = the same 1 048 576 aircraft sharded over the ranks (BASELINE's whole-node figure); "
-                         "weak = 1 048 576 aircraft per rank. The other mode is measured too and attached as an extra key")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[3] / configs[4] legs (1-GPU runs)")
+                         "weak = 1 048 576 aircraft per rank. With --full the other mode is measured too and attached as an extra key")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: CPU baseline, parity sample vs the oracle, the other scaling mode (N > 1), "
+                         "the configs[3] / configs[4] legs (off by default: a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity sample (a plain run leaves them out anyway)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the configs[3] / configs[4] legs (a plain run leaves them out anyway)")
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                     help="f64: the parity path (default, BASELINE.json's metric). f32: the fp32 airborne stepper (config 5's dtype)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (a fixed sample of the aircraft) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -579,19 +614,28 @@ def main():
     import flightbatch as fb
 
     scaling = args.scaling or "strong"   # (N > 1 only; BASELINE.json: "whole node at N = 1M")
+    head_mode = scaling if world > 1 else "weak"
+    modes = (head_mode,)
+    if world > 1 and args.full:
+        modes += ("weak" if scaling == "strong" else "strong",)
     results = {}
-    for mode in ((scaling, "weak" if scaling == "strong" else "strong") if world > 1 else ("weak",)):
+    for mode in modes:
+        lo = 0
         if mode == "strong":
             EAS, h, psi, cell = lattice(0)
             lo, hi = fb.sharding.shard_range(N_TOTAL, rank, world)
             EAS, h, psi, cell = EAS[lo:hi], h[lo:hi], psi[lo:hi], cell[lo:hi]
         else:
             EAS, h, psi, cell = lattice(rank)
-        m = time_c172s0(fb, torch, dist, C, EAS, h, psi, args, local_rank, world)
+        dump = args.dump_outputs is not None and mode == head_mode and rank == 0
+        m = time_c172s0(fb, torch, dist, C, EAS, h, psi, args, local_rank, world, dump=dump)
         m["cell"] = cell
         check_valid(m, mode)
+        if dump:   # (after the validity check: no outputs of a run that reports no throughput)
+            m["outputs"]["index"] += lo
+            write_outputs(args.dump_outputs, m.pop("outputs"))
         results[mode] = m
-    head = results[scaling if world > 1 else "weak"]
+    head = results[head_mode]
 
     line = None
     if rank == 0:
@@ -647,7 +691,7 @@ def main():
                        "checked_on_all_aircraft": "status == 0, fuel strictly decreasing, | |q| - 1 | <= " + ("1e-8" if args.dtype == "f64" else "5e-7") + " (q_wb, q_ew), all states finite"},
             "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS,
                          "traffic": traffic, "kernel_ms_median": head["launch_stats"]["kernel_ms"], "kernel_ms_min": head["launch_stats"]["kernel_ms_min"],
-                         "kernel_ms_max": head["launch_stats"]["kernel_ms_max"], "kernel": (("fbd::k_step_duo<0, false, false>" if os.environ.get("FLIGHTBATCH_DUO", "1") != "0" else "fbd::k_step_air<0, false, false, false>") if args.dtype == "f64" else "fbf::k_step_f32") + " (+ the ground-capable pass behind it)", "kernel_ms": kernel_ms,
+                         "kernel_ms_max": head["launch_stats"]["kernel_ms_max"], "launches_timed": head["launch_stats"]["launches_timed"], "kernel": (("fbd::k_step_duo<0, false, false>" if os.environ.get("FLIGHTBATCH_DUO", "1") != "0" else "fbd::k_step_air<0, false, false, false>") if args.dtype == "f64" else "fbf::k_step_f32") + " (+ the ground-capable pass behind it)", "kernel_ms": kernel_ms,
                          "note": f"algorithmic bytes = {bytes_per_unit:.0f} B per aircraft-step (SURVEY §8d" + ("" if args.dtype == "f64" else ", fp32 rows; q_ew / h_e stay fp64") + ") x N x inner steps per launch; the fused "
                                  "stepper is " + ("fp64" if args.dtype == "f64" else "fp32") + "-VALU-bound, see roofline_valu and DESIGN.md"},
             "roofline_valu": valu,
@@ -658,6 +702,7 @@ def main():
             per = head["elapsed_per_rank"]
             line["gather_ms"] = head["gather_ms"]
             line["ms_per_step_ranks"] = {"min": min(per) / args.steps * 1e3, "max": max(per) / args.steps * 1e3}
+        if world > 1 and args.full:
             other = results["weak" if scaling == "strong" else "strong"]
             line[("weak" if scaling == "strong" else "strong") + "_scaling"] = {
                 "value": float(other["n_total"]) * args.inner * args.steps / other["elapsed"], "unit": "aircraft-steps/s",
@@ -666,7 +711,7 @@ def main():
     # every GPU-timed leg runs BEFORE the CPU legs (the ~20 s of oracle work leave the GPU idle: round 5's driver run timed configs[3]
     # behind them with two warm-up launches and got 15.1 ms where 9.85 is the kernel's time — profiles/r06_x2_repro.txt)
     x2_timed = x2_lat = fleet_timed = None
-    extras = not args.no_extra and args.dtype == "f64"
+    extras = args.full and not args.no_extra and args.dtype == "f64"
     if extras:
         x2_timed = time_x2(fb, torch, dist, C, args, local_rank, world)   # configs[3]: one GPU's share, or this node's split with every rank taking part
     if world > 1:
@@ -676,16 +721,16 @@ def main():
         x2_lat = time_x2(fb, None, None, C, args, divergent=True)
         fleet_timed = extra_fleet(fb, C, args)
     if rank == 0:
-        # the CPU baseline and the parity sample ride on every line, multi-GPU ones included: rank 0, on its own shard, after the
-        # process group is gone (nothing of this is inside a timed region)
-        if not args.no_cpu_baseline:
+        # with --full, the CPU baseline and the parity sample ride on every line, multi-GPU ones included: rank 0, on its own shard,
+        # after the process group is gone (nothing of this is inside a timed region)
+        if args.full and not args.no_cpu_baseline:
             x0, s0, u0, ui0 = head["ic"]
             line["cpu_baseline"] = cpu_baseline(x0, u0, ui0, s0)
             line["rel_err_vs_cpu"] = parity_sample(fb, x0, u0, ui0, s0, head["cell"], args.dtype)
             if world > 1:
                 line["cpu_baseline"]["sample"] += f"; timed on rank 0's host share while the other {world - 1} ranks idle"
                 line["rel_err_vs_cpu"]["sample"] += " (rank 0's shard)"
-        if not args.no_extra and args.dtype == "f64":
+        if extras:
             head.pop("ic", None)
             line["extra"] = {"x2": extra_x2(fb, C, args, x2_timed)}
             if world == 1:

@@ -1,10 +1,12 @@
 """CPU checks of bench.py's host-side helpers: the benchmark lattice, the stratified parity sample, the per-launch statistics the bench line
-carries since round 6, and the command-line defaults the driver relies on."""
+carries since round 6, the command-line defaults the driver relies on, and the sample --dump-outputs writes; one GPU run of a plain bench.py."""
+import json
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -50,3 +52,68 @@ def test_command_line_defaults():
     assert "--gpus" in out and "--steps" in out and "--warmup" in out and "strong (default)" in out
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'scaling = args.scaling or "strong"' in src and 'PROFILE_COUNTERS = "r06_counters.json"' in src
+
+
+def test_full_and_dump_outputs_options():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True).stdout
+    assert "--full" in out and "--dump-outputs DIR" in out
+
+
+def test_output_sample_is_fixed_and_within_64_mb(fb):
+    b = _bench()
+    sel = b.output_sample(b.N_TOTAL)
+    assert np.array_equal(sel, b.output_sample(b.N_TOTAL)), "the same aircraft on every run"
+    assert sel.size == b.OUTPUT_SAMPLE and np.unique(sel).size == sel.size and np.all(np.diff(sel) > 0)
+    assert sel.min() < b.N_TOTAL * 0.01 and sel.max() > b.N_TOTAL * 0.99
+    assert np.array_equal(b.output_sample(1000), np.arange(1000))
+    rows = fb.K["FB_NX"] + fb.K["FB_NS"] + 2                          # x, s, status, index
+    assert rows * 8 * sel.size <= 64 << 20
+
+
+def test_sample_outputs_and_write_outputs(tmp_path):
+    b = _bench()
+    n, sel = 50, np.array([3, 7, 41])
+    x = np.random.default_rng(0).normal(size=(27, n))
+    s = np.arange(2 * n, dtype=np.int32).reshape(2, n)
+    st = (np.arange(n) % 3).astype(np.int32)
+    o = b.sample_outputs(x, s, st, sel)
+    b.write_outputs(str(tmp_path / "out"), o)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == ["index", "s", "status", "x"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x"], x[:, sel]) and np.array_equal(got["s"], s[:, sel])
+    assert np.array_equal(got["status"], st[sel]) and np.array_equal(got["index"], sel)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_its_outputs(tmp_path, fb):
+    """the headline only: --steps timed launches, ms_per_step on the line, no --full legs; the outputs of the last step on disk — the
+    sampled aircraft flown again here through the same 1 warm-up + 3 timed launches land where the dump says, one launch beyond 3"""
+    d = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["roofline"]["launches_timed"] == 3 and line["roofline"]["kernel_ms"] > 0 and line["ms_per_step"] >= line["roofline"]["kernel_ms_min"]
+    assert line["value"] > 0 and line["unit"] == "aircraft-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert "cpu_baseline" not in line and "rel_err_vs_cpu" not in line and "extra" not in line
+    b = _bench()
+    x, s, st, idx = (np.load(d / f"{k}.npy") for k in ("x", "s", "status", "index"))
+    assert x.shape == (27, b.OUTPUT_SAMPLE) and s.shape == (2, b.OUTPUT_SAMPLE) and sorted(os.listdir(d)) == ["index.npy", "s.npy", "status.npy", "x.npy"]
+    assert np.array_equal(idx, b.output_sample(b.N_TOTAL)) and (st == 0).all() and np.isfinite(x).all()
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    sel = idx.astype(np.int64)
+    EAS, h, psi, _ = b.lattice(0)
+    w = fb.BatchedWorld(sel.size)
+    fb.f_init(w, fb.TrimParameters(EAS=EAS[sel], h_e=h[sel], ψ_nb=psi[sel]))
+    sim = fb.Simulation(w, dt=b.DT, save_on=False, steps_per_launch=50)
+    for _ in range(3):
+        fb.step(sim, 50 * b.DT)
+    w.sync()
+    x3 = w.x
+    fb.step(sim, 50 * b.DT)
+    w.sync()
+    x4 = w.x
+    w.close()
+    assert (x[8] < x3[8]).all(), "fuel after the last timed launch is below what it is one launch earlier"
+    assert b.scaled_error(x, x4).max() < 1e-9, "the dump is the state after warm-up + timed launches"

@@ -16,8 +16,8 @@ cp gpurun_out/prof_$TAG/summary/* $OUT/
 cp gpurun_out/prof_$TAG/summary/${TAG}_counters.json $ROOT/profiles/
 bash tools/collect_profile_x2.sh $TAG > $OUT/collect_x2.log 2>&1; cp gpurun_out/prof_x2_$TAG/${TAG}_x2_counters.json $OUT/; cp gpurun_out/prof_x2_$TAG/${TAG}_x2_counters.json $ROOT/profiles/; echo "x2 pmc done"
 bash tools/collect_profile_f32.sh > $OUT/collect_f32.log 2>&1; cp gpurun_out/prof_f32pmc/r01_f32_counters.json $OUT/${TAG}_f32_counters.json; echo "profile f32 done"
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench f64 done"
-python3 bench.py --dtype f32 > $OUT/${TAG}_f32_bench.json 2> $OUT/bench_f32.err; echo "bench f32 done"
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench f64 done"
+python3 bench.py --full --dtype f32 > $OUT/${TAG}_f32_bench.json 2> $OUT/bench_f32.err; echo "bench f32 done"
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_f32 -- python3 $ROOT/bench.py --dtype f32 --steps 10 --warmup 2 --no-cpu-baseline --no-extra > $OUT/f32_under_rocprof.json 2> $OUT/stats_f32.log)
 cp $OUT/stats_f32/*/*_kernel_stats.csv $OUT/${TAG}_f32_kernel_stats.csv
 python3 tools/bench_x2.py > $OUT/${TAG}_x2_bench.json 2> $OUT/bench_x2.err

@@ -13,8 +13,8 @@ echo "== (b) 25 s idle in front, 2 warm-up launches (round 5's bench.py), 30 tim
 python3 tools/bench_x2.py --no-parity --pre-sleep 25 --warm-cap 2 --blocks 30 >> $OUT/r06_x2_repro.txt 2>&1
 echo "== (c) 25 s idle in front, warm-up until three launches agree within 1 % (cap 30), 12 timed" >> $OUT/r06_x2_repro.txt
 python3 tools/bench_x2.py --no-parity --pre-sleep 25 >> $OUT/r06_x2_repro.txt 2>&1
-echo "== (d) the driver's command" >> $OUT/r06_x2_repro.txt
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
+echo "== (d) the driver's command with every leg of the bench line (--full)" >> $OUT/r06_x2_repro.txt
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
 python3 - >> $OUT/r06_x2_repro.txt <<PY
 import json
 d = json.loads(open("$OUT/bench_driver_cmd.json").read().strip().splitlines()[-1])
