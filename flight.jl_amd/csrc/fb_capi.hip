@@ -11,6 +11,7 @@
 #include "c172_kernels_f32.hpp"
 #include "robot2d_kernels.hpp"
 #include "scenario_kernels.hpp"
+#include "lin_kernels.hpp"
 
 using namespace fbd;
 
@@ -86,6 +87,8 @@ struct fb_handle_s {
     // scripted scenario (FB_TABLE_SCENARIO): the program blob and the per-aircraft rows, all in device memory
     double* scn_prog = nullptr; int scn_nph = 0, scn_nrule = 0, scn_nact = 0, scn_npar = 0, scn_nrec = 0, scn_every = 0;
     int32_t* scn_phase = nullptr; long long* scn_since = nullptr; double* scn_par = nullptr; double* scn_rec = nullptr;
+    // fb_linearize / fb_linearize_state: device rows of the results (ẋ0 x0 u0 y0 | A B | C D) and the status OR, kept and grown on demand
+    double* lin_buf = nullptr; size_t lin_doubles = 0; int32_t* lin_st = nullptr;
 };
 
 static KArgs make_args(fb_handle h) {
@@ -396,6 +399,45 @@ static int32_t scn_evaluate(fb_handle h) {
     return 0;
 }
 
+// f_init!(aircraft, trim_params) under the environment `a` carries (fb_trim: the handle's; fb_linearize: still air): the trim solve, the
+// conversion to the handle's mechanisation, Cessna172Xv2's actuators and control laws; init! semantics (clock, terminations)
+static int32_t trim_run(fb_handle h, const KArgs& a, const double* trim_params, double* trim_state, int32_t* success, double* cost) {
+    const int64_t n = h->n;
+    if (!h->trim_buf) {
+        HIPCHK(hipMalloc(&h->trim_buf, sizeof(double) * ((FB_NTP + FB_NTS + 1) * n + 1)));   // (+ k_trim's queue position)
+        HIPCHK(hipMalloc(&h->trim_ok, sizeof(int32_t) * n));
+    }
+    double* d_tp = h->trim_buf;
+    double* d_ts = d_tp + (int64_t)FB_NTP * n;
+    double* d_cost = d_ts + (int64_t)FB_NTS * n;
+    HIPCHK(hipMemcpyAsync(d_tp, trim_params, sizeof(double) * FB_NTP * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_ts, trim_state, sizeof(double) * FB_NTS * n, hipMemcpyHostToDevice, h->stream));
+    // a persistent kernel: one wave per SIMD (k_trim holds the whole register file), aircraft taken from a queue
+    unsigned long long* d_next = reinterpret_cast<unsigned long long*>(d_cost + n);
+    HIPCHK(hipMemsetAsync(d_next, 0, sizeof(unsigned long long), h->stream));
+    int n_cu = 0;
+    HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    const int64_t trim_waves = std::min<int64_t>((n + 63) / 64, (int64_t)n_cu * 4);
+    if (!h->trim_ws) HIPCHK(hipMalloc(&h->trim_ws, sizeof(double) * fbd::TRIM_WS_ROWS * 64 * trim_waves));
+    if (a.env_rows) hipLaunchKernelGGL(k_trim<true>, dim3((unsigned)trim_waves), dim3(64), 0, h->stream, a, (const double*)d_tp, d_ts, h->trim_ok, d_cost, d_next, h->trim_ws);
+    else hipLaunchKernelGGL(k_trim<false>, dim3((unsigned)trim_waves), dim3(64), 0, h->stream, a, (const double*)d_tp, d_ts, h->trim_ok, d_cost, d_next, h->trim_ws);
+    HIPCHK(hipGetLastError());
+    if (h->kin == FB_KIN_ECEF) hipLaunchKernelGGL(k_kin_convert<FB_KIN_ECEF>, grid_for(n, 256), dim3(256), 0, h->stream, a, (const double*)d_tp);
+    if (h->kin == FB_KIN_NED) hipLaunchKernelGGL(k_kin_convert<FB_KIN_NED>, grid_for(n, 256), dim3(256), 0, h->stream, a, (const double*)d_tp);
+    if (is_x2(h)) {  // f_init!(aircraft, trim): actuator states, then f_init!(avionics, vehicle) (aircraftbase.jl:255-265)
+        FB_LAUNCH_X2K(k_x2_init, n, a, ctl_args(h, 0));
+        HIPCHK(hipGetLastError());
+    }
+    h->steps_done = 0;
+    HIPCHK(clear_terminations(h));
+    HIPCHK(hipMemcpyAsync(trim_state, d_ts, sizeof(double) * FB_NTS * n, hipMemcpyDeviceToHost, h->stream));
+    if (success) HIPCHK(hipMemcpyAsync(success, h->trim_ok, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    if (cost) HIPCHK(hipMemcpyAsync(cost, d_cost, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->t = 0.0;
+    return 0;
+}
+
 extern "C" {
 
 const char* fb_last_error(void) { return g_err.c_str(); }
@@ -442,6 +484,7 @@ int32_t fb_destroy(fb_handle h) {
     hipFree(h->x_own); hipFree(h->s_own); hipFree(h->u); hipFree(h->ui); hipFree(h->status); hipFree(h->term_step); hipFree(h->term_where); hipFree(h->y); hipFree(h->xdot);
     hipFree(h->tables); hipFree(h->tables_f32); hipFree(h->egm96); hipFree(h->trim_buf); hipFree(h->trim_ok); hipFree(h->trim_ws); hipFree(h->env_rows);
     hipFree(h->cs); hipFree(h->cu); hipFree(h->q_pre); hipFree(h->ctl_bak); hipFree(h->duo_pld); hipFree(h->duo_tap); hipFree(h->gains); hipFree(h->redo); hipFree(h->k1); hipFree(h->k1_valid);
+    hipFree(h->lin_buf); hipFree(h->lin_st);
     hipEventDestroy(h->ev0); hipEventDestroy(h->ev1);
     for (hipEvent_t e : h->lev) hipEventDestroy(e);
     hipStreamDestroy(h->own_stream);
@@ -704,40 +747,7 @@ int32_t fb_trim(fb_handle h, const double* trim_params, double* trim_state, int3
     if (int32_t rc = check_ready_x2(h)) return rc;
     if (!trim_params || !trim_state) return fail("null argument");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n;
-    if (!h->trim_buf) {
-        HIPCHK(hipMalloc(&h->trim_buf, sizeof(double) * ((FB_NTP + FB_NTS + 1) * n + 1)));   // (+ k_trim's queue position)
-        HIPCHK(hipMalloc(&h->trim_ok, sizeof(int32_t) * n));
-    }
-    double* d_tp = h->trim_buf;
-    double* d_ts = d_tp + (int64_t)FB_NTP * n;
-    double* d_cost = d_ts + (int64_t)FB_NTS * n;
-    HIPCHK(hipMemcpyAsync(d_tp, trim_params, sizeof(double) * FB_NTP * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_ts, trim_state, sizeof(double) * FB_NTS * n, hipMemcpyHostToDevice, h->stream));
-    // a persistent kernel: one wave per SIMD (k_trim holds the whole register file), aircraft taken from a queue
-    unsigned long long* d_next = reinterpret_cast<unsigned long long*>(d_cost + n);
-    HIPCHK(hipMemsetAsync(d_next, 0, sizeof(unsigned long long), h->stream));
-    int n_cu = 0;
-    HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-    const int64_t trim_waves = std::min<int64_t>((n + 63) / 64, (int64_t)n_cu * 4);
-    if (!h->trim_ws) HIPCHK(hipMalloc(&h->trim_ws, sizeof(double) * fbd::TRIM_WS_ROWS * 64 * trim_waves));
-    if (h->env_rows) hipLaunchKernelGGL(k_trim<true>, dim3((unsigned)trim_waves), dim3(64), 0, h->stream, make_args(h), (const double*)d_tp, d_ts, h->trim_ok, d_cost, d_next, h->trim_ws);
-    else hipLaunchKernelGGL(k_trim<false>, dim3((unsigned)trim_waves), dim3(64), 0, h->stream, make_args(h), (const double*)d_tp, d_ts, h->trim_ok, d_cost, d_next, h->trim_ws);
-    HIPCHK(hipGetLastError());
-    if (h->kin == FB_KIN_ECEF) hipLaunchKernelGGL(k_kin_convert<FB_KIN_ECEF>, grid_for(n, 256), dim3(256), 0, h->stream, make_args(h), (const double*)d_tp);
-    if (h->kin == FB_KIN_NED) hipLaunchKernelGGL(k_kin_convert<FB_KIN_NED>, grid_for(n, 256), dim3(256), 0, h->stream, make_args(h), (const double*)d_tp);
-    if (is_x2(h)) {  // f_init!(aircraft, trim): actuator states, then f_init!(avionics, vehicle) (aircraftbase.jl:255-265)
-        FB_LAUNCH_X2K(k_x2_init, n, make_args(h), ctl_args(h, 0));
-        HIPCHK(hipGetLastError());
-    }
-    h->steps_done = 0;
-    HIPCHK(clear_terminations(h));
-    HIPCHK(hipMemcpyAsync(trim_state, d_ts, sizeof(double) * FB_NTS * n, hipMemcpyDeviceToHost, h->stream));
-    if (success) HIPCHK(hipMemcpyAsync(success, h->trim_ok, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
-    if (cost) HIPCHK(hipMemcpyAsync(cost, d_cost, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->t = 0.0;
-    return 0;
+    return trim_run(h, make_args(h), trim_params, trim_state, success, cost);
 }
 
 int32_t fb_f_ode(fb_handle h, double* xdot) {
@@ -1179,4 +1189,5 @@ int32_t fb_timing_end(fb_handle h, float* ms, int64_t* n_launches) {
 }  // extern "C"
 
 #include "fb_comm.inc"
+#include "fb_lin.inc"
 

@@ -14,3 +14,4 @@ from .c172x import Cessna172Xv2World, ModeControlLon, ModeControlLat, ModeGuidan
 from . import ctl_gains  # noqa: F401
 from . import scenario  # noqa: F401
 from .fleet import MixedFleet  # noqa: F401
+from .linearization import LinearizedSS, linearize, linearize_state, subsystem, delete_vars  # noqa: F401

@@ -47,6 +47,9 @@ def _load():
         "fb_get_inputs": ([H, D, I32], C.c_int32),
         "fb_trim": ([H, D, D, I32, D], C.c_int32),
         "fb_f_ode": ([H, D], C.c_int32),
+        "fb_linearize_dims": ([H, I32, I32, I32], C.c_int32),
+        "fb_linearize": ([H, D, D, I32, D, C.c_int32, D, D, D, D, D, D, D, D, I32], C.c_int32),
+        "fb_linearize_state": ([H, C.c_int32, D, D, D, D, D, D, D, D, I32], C.c_int32),
         "fb_f_step": ([H], C.c_int32),
         "fb_f_periodic": ([H], C.c_int32),
         "fb_get_outputs": ([H, D], C.c_int32),

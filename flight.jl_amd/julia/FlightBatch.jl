@@ -29,6 +29,7 @@ using Flight.FlightPhysics: Propellers, Piston, Control
 using Flight.FlightPhysics.Kinematics: WA, ECEF, NED                   # kinematic descriptors (exported at FP/kinematics.jl:11)
 using Flight.FlightApps.C172.C172S.C172Sv0: Cessna172Sv0               # FA/c172/c172s/c172s0.jl:9,14-18
 using Flight.FlightApps.C172.C172X.C172Xv2: Cessna172Xv2               # FA/c172/c172x/c172x2.jl:12,54-59
+import Flight.FlightPhysics.Linearization: linearize                   # FP/linearization.jl:8
 
 const lib = get(ENV, "FLIGHTBATCH_LIB", "libflightbatch")
 
@@ -210,6 +211,31 @@ function f_init!(w::BatchedWorld, trim::C172.TrimParameters)
     check(ccall((:fb_trim, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}), w.handle, tp, ts, ok, cost))
     all(==(1), ok) || @warn("Trimming failed for $(count(!=(1), ok)) aircraft")    # c172.jl:936-938
     return nothing
+end
+"""linearize(world, C172.TrimParameters(); scheme = 0) — `linearize(aircraft, trim_params)` (FP/aircraftbase.jl:292-334) for every aircraft at
+once: still-air trim, then ẋ0, x0, u0, y0 and the four matrices a, b, c, d (forward differences, FiniteDiff's steps, with scheme = 0 = FB_LIN_FORWARD). The
+matrices come back as [N, rows, cols] arrays; wrap one aircraft's slices in `LinearizedSS` (FP/linearization.jl:39-48) for labelled axes."""
+function linearize(w::BatchedWorld, trim::C172.TrimParameters; scheme::Integer = 0)
+    tp = Matrix{Float64}(undef, w.n, NTP)
+    tp[:, 1:3] .= trim.Ob.loc[:]'; tp[:, 4] .= Float64(trim.Ob.h); tp[:, 5] .= trim.ψ_nb; tp[:, 6] .= trim.EAS
+    tp[:, 7] .= trim.γ_wb_n; tp[:, 8] .= trim.ψ_wb_dot; tp[:, 9] .= trim.θ_wb_dot; tp[:, 10] .= trim.β_a
+    tp[:, 11] .= Float64(trim.fuel_load); tp[:, 12] .= Float64(trim.mixture); tp[:, 13] .= Float64(trim.flaps)
+    p = trim.payload
+    tp[:, 14:18] .= Float64[Float64(p.m_pilot) Float64(p.m_copilot) Float64(p.m_lpass) Float64(p.m_rpass) Float64(p.m_baggage)]
+    ts = repeat(collect(C172.TrimState())', w.n)
+    ok = Vector{Int32}(undef, w.n); cost = Vector{Float64}(undef, w.n)
+    nx, nu, ny = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+    check(ccall((:fb_linearize_dims, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}), w.handle, nx, nu, ny))
+    nx, nu, ny = nx[], nu[], ny[]
+    xdot0 = Matrix{Float64}(undef, w.n, nx); x0 = similar(xdot0); u0 = Matrix{Float64}(undef, w.n, nu); y0 = Matrix{Float64}(undef, w.n, ny)
+    a = Array{Float64}(undef, w.n, nx, nx); b = Array{Float64}(undef, w.n, nx, nu)
+    c = Array{Float64}(undef, w.n, ny, nx); d = Array{Float64}(undef, w.n, ny, nu)
+    status = Vector{Int32}(undef, w.n)
+    check(ccall((:fb_linearize, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, tp, ts, ok, cost, scheme, xdot0, x0, u0, y0, a, b, c, d, status))
+    all(==(1), ok) || @warn("Trimming failed for $(count(!=(1), ok)) aircraft")
+    return (; xdot0, x0, u0, y0, a, b, c, d, status, success = ok .== 1, cost)   # a, b, c, d: A, B, C, D
 end
 f_ode!(w::BatchedWorld) = (check(ccall((:fb_f_ode, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, C_NULL)); nothing)
 f_step!(w::BatchedWorld) = (check(ccall((:fb_f_step, lib), Cint, (Ptr{Cvoid},), w.handle)); nothing)

@@ -294,6 +294,34 @@ int32_t fb_trim(fb_handle h, const double* trim_params, double* trim_state, int3
  * then f_init!(avionics, vehicle). */
 int32_t fb_f_init(fb_handle h, const double* init, int32_t ninit);
 
+/* ---- linearize (FP/linearization.jl:55-148, FP/aircraftbase.jl:292-334, FA/robot2d/robot2d.jl:233-341) ---------------------------
+ * The state-space vectors x_ss / u_ss / y_ss of get_x_ss / get_u_ss / get_y_ss: Cessna172Sv0(NED) 16 / 4 / 33 (FA/c172/c172s/c172s.jl:269-412),
+ * Cessna172Xv2(NED) 20 / 4 / 38 (its vehicle, FA/c172/c172x/c172x.jl:332-490: u_ss = the four actuator COMMANDS, substituted where the
+ * actuators read them; avionics take no part), Robot2D 4 / 1 / 6 (robot2d.jl:233-275). WA / ECEF Cessnas and FB_F32 handles have none.
+ * Outputs in the ABI's convention, aircraft index fastest: xdot0, x0 [N x nx], u0 [N x nu], y0 [N x ny]; the matrices column-major per
+ * aircraft: element (i, r, c) of A [N x nx x nx] at A[(r + nx c) N + i], B [N x nx x nu], C [N x ny x nx], D [N x ny x nu]. Every output
+ * pointer may be NULL (a NULL block is not copied; with A, B or C, D both NULL that half is not written on the device either).
+ * lin_status[i] = the OR of the FB_ST_* bits of every evaluation of aircraft i (where the reference would throw out of linearize).
+ * Schemes: FB_LIN_FORWARD = FiniteDiff's default forward Jacobian, the reference's: step max(2^-26 |z|, 2^-26), (f(z + e) - f(z)) / e,
+ * 1 + nx + nu evaluations per aircraft; FB_LIN_ONESIDED2 = (-3 f(z) + 4 f(z + h) - f(z + 2h)) / 2h with h = (z + 1e-6 max(|z|, 1)) - z,
+ * 1 + 2 (nx + nu) evaluations, ~1e-10 instead of ~1e-8 (docs/design/linearize.md). Host copy of a full result: 8 x (2 nx + nu + ny +
+ * (nx + ny)(nx + nu)) bytes per aircraft (Cessna172Sv0: 8.4 KB). */
+enum { FB_LIN_FORWARD = 0, FB_LIN_ONESIDED2 = 1 };
+/* nx, nu, ny of get_x_ss / get_u_ss / get_y_ss for this handle's vehicle (refuses handles that have none) */
+int32_t fb_linearize_dims(fb_handle h, int32_t* nx, int32_t* nu, int32_t* ny);
+/* linearize(vehicle, trim_params): FP/aircraftbase.jl:292-334, FA/robot2d/robot2d.jl:315-341.
+ * Cessna: params = trim parameters [N x FB_NTP], trim_state [N x FB_NTS] in/out, success / cost as fb_trim. The trim runs in the reference's
+ * own environment — ISA sea level, no wind, terrain elevation 0, DryTarmac — whatever fb_set_params / fb_set_env say (those stay in place,
+ * unused by this call); the handle is left as fb_trim leaves it after a still-air trim (x, s, u, Cessna172Xv2's control laws, clock,
+ * status words, termination record). Robot2D: params = InitParameters [N x 3] (NULL: the defaults), trim_state / success / cost unused;
+ * the handle is left as fb_f_init leaves it. */
+int32_t fb_linearize(fb_handle h, const double* params, double* trim_state, int32_t* success, double* cost, int32_t scheme,
+                     double* xdot0, double* x0, double* u0, double* y0, double* A, double* B, double* C, double* D, int32_t* lin_status);
+/* linearize(f, h, x0, u0) at the handle's CURRENT x, u, s (Cessna172Xv2: the commands in its control-law record) and environment
+ * (fb_params block or fb_set_env rows, as fb_f_ode): FP/linearization.jl:55-111. Changes nothing on the handle. */
+int32_t fb_linearize_state(fb_handle h, int32_t scheme, double* xdot0, double* x0, double* u0, double* y0,
+                           double* A, double* B, double* C, double* D, int32_t* lin_status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
