@@ -339,6 +339,16 @@ FBD double x2_command(const KArgs& a, int64_t i, int k) { return x2_command_sat(
 #ifndef FB_X2_BAK
 #define FB_X2_BAK 1
 #endif
+// Launches of up to FB_CTL_BAK_SKIP steps take neither the launch-start copy of the control-law record nor its way back: one step only (the
+// argument is at k_step_air's copy). -DFB_CTL_BAK_DEFECT rebuilds the defect this guards against — no copy up to seven steps, where a lane is
+// handed over behind control updates of its own launch — so that the tests can be seen to fail on it: tests/test_gpu_launch_edges.py,
+// profiles/r07_launch_edge_defects.txt. (Likewise -DFB_K1_VALID_DEFECT at k_step_duo's epilogue and -DFB_CRASH_CTL_DEFECT at k_step_air's
+// control update.)
+#ifdef FB_CTL_BAK_DEFECT
+#define FB_CTL_BAK_SKIP 7
+#else
+#define FB_CTL_BAK_SKIP 1
+#endif
 #ifndef FB_X2_BAK_G_CS
 #define FB_X2_BAK_G_CS 11
 #endif
@@ -725,8 +735,9 @@ restart:
         // (a launch of ONE step needs neither the copy nor the way back: its only control update is the last thing it does — behind the step's last
         // evaluation and f_step!, with no re-evaluation of k1 behind it in this launch — so a lane that is handed over, or that throws, has not had
         // one. At one step per launch, the shape of every host callback and of a scenario table evaluated after every step, the two copies were
-        // 1.5 KB per aircraft and launch, as much again as the state and the record the step itself moves.)
-        if (a.ctl_ratio > 0 && nsteps > 1 && mine) {
+        // 1.5 KB per aircraft and launch, as much again as the state and the record the step itself moves. Held by tests/test_gpu_launch_edges.py
+        // and the one-step cases of tests/test_gpu_termination.py's Cessna172Xv2 tests: hand-overs and throws at 1, 7 and 50 steps per launch.)
+        if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP && mine) {
             if (!replaying) {
                 copy_rows_batched<FB_NCS, 11>(a.ctl_bak, a.cs, a.n, il);
                 copy_rows_batched<FB_NCU, 14>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, il);
@@ -897,7 +908,11 @@ restart:
             const bool ctl_now = X && a.ctl_ratio > 0 && (a.ctl_phase + step) % a.ctl_ratio == 0;   // wave-uniform
             if (run) {
                 if constexpr (X) {
+#ifdef FB_CRASH_CTL_DEFECT   // (rebuilds the defect the guard is there for: the update runs for a lane f_step! is about to terminate; see FB_CTL_BAK_SKIP)
+                    if (ctl_now) {
+#else
                     if (ctl_now && !aux.crash) {
+#endif
                         CtlIn v;
                         {
                             const CtlSink tv = tap_values(tap);
@@ -1012,7 +1027,7 @@ restart:
     }
     if (!GROUND && handoff) {
         if constexpr (X) {
-            if (a.ctl_ratio > 0 && nsteps > 1) {   // nothing of this lane's launch is committed: undo the control-law updates it has made (one step: it has made none)
+            if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP) {   // nothing of this lane's launch is committed: undo the control-law updates it has made (one step: it has made none)
 #pragma unroll 1
                 for (int k = 0; k < FB_NCS; k++) a.cs[(int64_t)k * a.n + i] = a.ctl_bak[(int64_t)k * a.n + i];
 #pragma unroll 1
@@ -1621,7 +1636,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 for (int k = 0; k < NAL; k++) { xa[k] = a.x[(int64_t)(X2_ACT + k) * a.n + i]; ca[k] = x2_command(a, i, k); }
                 in.mixture = clampd(a.u[(int64_t)FB_U_MIXTURE * a.n + i], 0, 1);
                 in.ui = a.ui[i];
-                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > 1) {   // its half of the launch-start copy of the control-law record (role D copies cu); not for a launch of one step: see k_step_air
+                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP) {   // its half of the launch-start copy of the control-law record (role D copies cu); not for a launch of one step: see k_step_air
                     static_assert(FB_NCS % 11 == 0 && FB_NCU % 14 == 0 && FB_NCS % FB_X2_BAK_G_CS == 0 && FB_NCU % FB_X2_BAK_G_CU == 0, "batch sizes of the record copies");
                     copy_rows_batched<FB_NCS, FB_X2_BAK_G_CS>(a.ctl_bak, a.cs, a.n, i);
                 }
@@ -1852,7 +1867,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     for (int k = 0; k < 10; k++) a.duo_pld[(int64_t)k * a.n + i] = pv[k];
                 }
                 in.ui = in0.ui;
-                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > 1 && !to_ground) {   // its half of the launch-start copy of the control-law record (role P copies cs)
+                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP && !to_ground) {   // its half of the launch-start copy of the control-law record (role P copies cs)
                     copy_rows_batched<FB_NCU, FB_X2_BAK_G_CU>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, i);
                 }
             } else {
@@ -2045,7 +2060,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     if (!(d & D_ACTIVE)) return;
     if (d & D_HANDOFF) {
         if constexpr (X) {
-            if (a.ctl_ratio > 0 && nsteps > 1) {   // nothing of this lane's launch is committed: undo the control-law updates it has made (both halves are at rest: point F)
+            if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP) {   // nothing of this lane's launch is committed: undo the control-law updates it has made (both halves are at rest: point F)
 #pragma unroll 1
                 for (int k = 0; k < FB_NCS; k++) a.cs[(int64_t)k * a.n + i] = a.ctl_bak[(int64_t)k * a.n + i];
 #pragma unroll 1
@@ -2060,7 +2075,9 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     // evaluation within reach of the ground) has not moved, and the pass that takes it over starts from the k1 it stored itself at the end of the
     // launch before. (Up to round 6 the flag was cleared at entry for every lane: the ground-capable pass then evaluated k1 again in EVERY launch —
     // five evaluations where four do in a one-step launch, the shape of every scenario table evaluated after each step; tools/stamp_ground_launch.py.)
+#ifndef FB_K1_VALID_DEFECT   // (-DFB_K1_VALID_DEFECT rebuilds the defect: the flag left set on commit, see FB_CTL_BAK_SKIP)
     if constexpr (X) { if (a.k1) a.k1_valid[i] = 0; }
+#endif
     bool bad = false;
 #pragma unroll
     for (int k = 0; k < FB_NX; k++) {

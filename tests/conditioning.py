@@ -37,9 +37,9 @@ def nudge(v, rel, sign):
 ULP_R = float(np.spacing(6.4e6))   # 2^-30 m: one ulp of the geocentric radius
 
 
-def x2_perturbed_runs(X, start, env, nsteps, h_row, h_runway, rel, K=4, jitter=0.0, chunk=10, reach=8.0, seed=0, threads=0):
+def x2_perturbed_runs(X, start, env, nsteps, h_row, h_runway, rel, K=4, jitter=0.0, chunk=10, reach=8.0, seed=0, threads=0, ratio=2):
     """K oracle runs of Cessna172Xv2 (OracleX dict `start`: x in ORACLE row order, u, ui, s, cu, cs) over nsteps steps at dt = 0.01,
-    Δt = 0.02, each with v_eb_b (oracle rows 24-26) nudged once per aircraft, at the first chunk boundary at which its altitude row is
+    Δt = ratio x 0.01, each with v_eb_b (oracle rows 24-26) nudged once per aircraft, at the first chunk boundary at which its altitude row is
     within `reach` metres of the runway, and — jitter > 0 — its altitude moved by +/- jitter at every step from there on. Returns the
     list of final dicts."""
     rng = np.random.default_rng(seed)
@@ -63,7 +63,7 @@ def x2_perturbed_runs(X, start, env, nsteps, h_row, h_runway, rel, K=4, jitter=0
             if jitter > 0 and near.any():
                 o["x"][h_row, near] += jitter * rng.choice([-1.0, 1.0], int(near.sum()))
             m = min(chunk, left)
-            X.step_term(o, env, 0.01, 2, m, threads=threads)
+            X.step_term(o, env, 0.01, ratio, m, threads=threads)
             left -= m
         o["nudged"] = done
         outs.append(o)

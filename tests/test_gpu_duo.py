@@ -2,6 +2,7 @@
 waves per SIMD, the default) and the one-wave-per-SIMD k_step_air (FLIGHTBATCH_DUO=0). Same physics, different evaluation order and fma
 contraction: they agree to rounding, lane by lane, including on the lanes that are not ordinary — beyond the end of a ragged batch,
 terminated before the launch, sitting on the ground, sinking through the hand-over clearance in the middle of a launch."""
+import contextlib
 import os
 
 import numpy as np
@@ -13,16 +14,23 @@ pytestmark = pytest.mark.gpu
 H_E_ROW = {"WA": 20, "ECEF": 19, "NED": 17}     # the ellipsoidal altitude in the C ABI's state of each mechanisation
 
 
-def _world(fb, n, duo, kin="WA"):
+@contextlib.contextmanager
+def stepper(duo):
+    """worlds created inside are stepped by k_step_duo (duo) or by the one-wave k_step_air (FLIGHTBATCH_DUO=0, read when a handle is created)"""
     old = os.environ.get("FLIGHTBATCH_DUO")
     os.environ["FLIGHTBATCH_DUO"] = "1" if duo else "0"
     try:
-        return fb.BatchedWorld(n, kinematics=kin)
+        yield
     finally:
         if old is None:
             del os.environ["FLIGHTBATCH_DUO"]
         else:
             os.environ["FLIGHTBATCH_DUO"] = old
+
+
+def _world(fb, n, duo, kin="WA"):
+    with stepper(duo):
+        return fb.BatchedWorld(n, kinematics=kin)
 
 
 def _scale(x):

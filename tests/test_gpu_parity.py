@@ -556,7 +556,9 @@ def test_ecef_and_ned_mechanisations(fb, oracle, kin):
 def test_approach_crosses_the_air_ground_handover(fb, oracle):
     """Descending approaches that start above the 10 m clearance limit of the airborne stepping instance and sink through it
     (some down to the runway) inside fused launches: the lanes handed over to the ground-capable instance must give the same
-    trajectory as the oracle, and the result must not depend on where the launch boundaries fall."""
+    trajectory as the oracle, and the result must not depend on where the launch boundaries fall — 50, 7 or 1 step per launch — nor on
+    which airborne stepper hands the lanes over (k_step_duo, or the one-wave k_step_air with FLIGHTBATCH_DUO=0)."""
+    from test_gpu_duo import stepper
     n = 1024
     rng = np.random.default_rng(17)
     h_trn = 300.0
@@ -564,8 +566,10 @@ def test_approach_crosses_the_air_ground_handover(fb, oracle):
                            flaps=1.0, ψ_nb=rng.uniform(-3, 3, n))
     env = oracle.default_env(h_trn=h_trn)
     results = []
-    for spl in (50, 7):
-        w = fb.BatchedWorld(n)
+    runs = [(50, True), (7, True), (1, True), (7, False)]   # (steps per launch, duo)
+    for spl, duo in runs:
+        with stepper(duo):
+            w = fb.BatchedWorld(n)
         w.set_params(h_terrain=h_trn)
         fb.f_init(w, tp)
         x0, s0, u0, ui0 = w.x, w.s, w.u, w.ui
@@ -589,10 +593,12 @@ def test_approach_crosses_the_air_ground_handover(fb, oracle):
     near = agl < 2.5          # has been (or is about to be) on its wheels: contact forces are conditioned to ~1e-7 (see above)
     print("approach, max scaled error after 600 steps: airborne %.2e, touched down %.2e" % (err[:, live & ~near].max(), err[:, live & near].max()))
     assert err[:, live & ~near].max() < 1e-6 and err[:, live & near].max() < 2e-5 and np.array_equal(sg[:, live], so[:, live])
-    # launch boundaries elsewhere: same trajectories to rounding (a lane is stepped by one instance or the other per launch)
-    x2, s2, st2 = results[1]
-    assert np.array_equal(st2[ok], stg[ok])
-    assert (np.abs(x2 - xg) / state_scale(xo))[:, live & ~near].max() < 1e-9
+    # launch boundaries elsewhere, the other airborne stepper: same trajectories to rounding (a lane is stepped by one instance or the other per launch)
+    for (spl, duo), (x2, s2, st2) in zip(runs[1:], results[1:]):
+        d = (np.abs(x2 - xg) / state_scale(xo))[:, live & ~near].max()
+        print(f"approach, {spl} steps per launch ({'duo' if duo else 'one-wave'}) against 50 (duo): max scaled difference, airborne {d:.2e}")
+        assert np.array_equal(st2[ok], stg[ok])
+        assert d < 1e-9, (spl, duo, d)
 
 
 @pytest.mark.parametrize("kin", ["WA", "ECEF", "NED"])

@@ -11,6 +11,7 @@ every aircraft of a batch driven into each termination:
     * and on everything that is still flying, as before.
 """
 import ctypes as C
+import hashlib
 
 import numpy as np
 import pytest
@@ -20,6 +21,7 @@ import conditioning
 from oracle_binding import OracleX
 from test_gpu_parity import lattice_trim_params, state_scale
 from test_gpu_c172x import ref_to_dev_rows, x_scale
+from test_gpu_duo import stepper
 
 pytestmark = pytest.mark.gpu
 _D = C.POINTER(C.c_double)
@@ -240,10 +242,30 @@ def test_robot2d_lost_balance_matches_oracle(fb, oracle):
     w.close()
 
 
-def test_x2_crash_under_autopilot(fb, oracle):
+# The Cessna172Xv2 termination tests run at these launch lengths, on both airborne steppers (duo: k_step_duo; air: the one-wave k_step_air,
+# FLIGHTBATCH_DUO=0), at Δt = 2 dt and — where every step closes a control period, so that the crash guard of the control update decides
+# every crash step — at Δt = dt. A launch of one step takes no copy of the control-law record (ctl_bak); seven steps do.
+X2_CASES = [(50, True, 2), (1, True, 1), (1, False, 1), (7, True, 2), (7, False, 2)]
+X2_IDS = [f"spl{s}-{'duo' if d else 'air'}-r{r}" for s, d, r in X2_CASES]
+_X2_ORACLE = {}   # (test, ratio, digest of the start state) -> the oracle's runs: once per ratio, not once per case
+
+
+def _x2_oracle(tag, ratio, start, make):
+    h = hashlib.sha256()
+    for k in sorted(start):
+        h.update(k.encode()); h.update(np.ascontiguousarray(start[k]).tobytes())
+    key = (tag, ratio, h.hexdigest())
+    if key not in _X2_ORACLE:
+        _X2_ORACLE[key] = make()
+    return _X2_ORACLE[key]
+
+
+@pytest.mark.parametrize("spl,duo,ratio", X2_CASES, ids=X2_IDS)
+def test_x2_crash_under_autopilot(fb, oracle, spl, duo, ratio):
     """Cessna172Xv2 flown into the ground by its own autopilot (EAS + climb-rate mode, a steep descent demanded over a runway 15-60 m
     below): GroundCrash out of f_step! at touchdown — no control-law update in that step (cb_step throws before cb_periodic,
-    sim.jl:204-218) — state, control-law record, status word, step and place against the oracle."""
+    sim.jl:204-218) — state, control-law record, status word, step and place against the oracle. (At one step per launch and Δt = dt
+    every crash step closes a control period: seen to fail on a library built with -DFB_CRASH_CTL_DEFECT, profiles/r07_launch_edge_defects.txt.)"""
     gains = fb.ctl_gains.ctl_gains_blob()
     K = fb.K
     n = 4096
@@ -251,13 +273,14 @@ def test_x2_crash_under_autopilot(fb, oracle):
     h_agl = rng.uniform(15.0, 60.0, n)
     N0 = geoid(oracle, np.zeros(1), np.zeros(1))[0]
     tp = fb.TrimParameters(EAS=rng.uniform(42.0, 55.0, n), h_e=N0 + 2.0 + h_agl, ψ_nb=rng.uniform(-np.pi, np.pi, n), γ_wb_n=-0.05)
-    w = fb.Cessna172Xv2World(n, gains=gains)
-    sim = fb.Simulation(w, dt=0.01, Δt=0.02, save_on=False, steps_per_launch=50)
+    with stepper(duo):
+        w = fb.Cessna172Xv2World(n, gains=gains)
+    sim = fb.Simulation(w, dt=0.01, Δt=0.01 * ratio, save_on=False, steps_per_launch=spl)
     fb.init(sim, tp)
     assert w.trim_success.all()
     X = OracleX(oracle, gains)
     env = oracle.default_env()
-    o = X.trim_init(tp.pack(n), fb.TrimState(n), env, 0.02)
+    o = X.trim_init(tp.pack(n), fb.TrimState(n), env, 0.01 * ratio)
     o["status"] = np.zeros(n, np.int32); o["nstep"] = 0
     cu = w.cu
     cu[K["FB_CU_LON_MODE_REQ"]] = float(fb.ModeControlLon.EAS_clm)
@@ -269,11 +292,20 @@ def test_x2_crash_under_autopilot(fb, oracle):
     o["x"][perm] = w.x; o["cs"] = w.cs; o["u"] = w.u; o["ui"] = w.ui; o["s"] = w.s
     fb.step(sim, 12.0); w.sync()
     o_start = {k: np.array(v, copy=True) for k, v in o.items() if isinstance(v, np.ndarray)}
-    X.step_term(o, env, 0.01, 2, 1200)
-    pert = conditioning.x2_perturbed_runs(X, o_start, env, 1200, 20, N0, 1e-12, K=4, jitter=conditioning.ULP_R, seed=3, threads=16)   # the oracle against itself, below
+    start = {k: o_start[k] for k in ("x", "cs", "cu", "u", "ui", "s")}
+
+    def run_oracle():
+        oo = {k: np.array(v, copy=True) for k, v in o_start.items()}
+        oo["nstep"] = 0
+        X.step_term(oo, env, 0.01, ratio, 1200)
+        pert = conditioning.x2_perturbed_runs(X, o_start, env, 1200, 20, N0, 1e-12, K=4, jitter=conditioning.ULP_R, seed=3, threads=16,
+                                              ratio=ratio)   # the oracle against itself, below
+        return oo, pert
+    o, pert = _x2_oracle("crash", ratio, start, run_oracle)
+    label = f"Xv2 under autopilot ({spl} steps per launch, {'duo' if duo else 'one-wave'}, Δt = {ratio} dt)"
     st, sto = w.status, o["status"]
     term = sto != 0
-    print("Xv2 under autopilot:", int(term.sum()), "of", n, "crashed; status words", np.unique(sto), "places", np.unique(o["term_where"]))
+    print(label + ":", int(term.sum()), "of", n, "crashed; status words", np.unique(sto), "places", np.unique(o["term_where"]))
     assert np.array_equal(st, sto)
     assert term.sum() >= 1000 and (~term).sum() >= 200
     tstep, twhere = w.termination
@@ -285,7 +317,7 @@ def test_x2_crash_under_autopilot(fb, oracle):
     he_row = int(np.where(perm == 20)[0][0])
     flying = ~term & (xo[he_row] - N0 > 8.0)          # still clear of the runway at the end
     rolling = ~term & ~flying                          # touched down hard, survived, and have been rolling / bouncing since
-    print("Xv2: max scaled state error, crashed", err[:, term].max(), "| still flying", err[:, flying].max() if flying.any() else 0.0,
+    print(label + ": max scaled state error, crashed", err[:, term].max(), "| still flying", err[:, flying].max() if flying.any() else 0.0,
           f"({int(flying.sum())}) | rolling", err[:, rolling].max() if rolling.any() else 0.0, f"({int(rolling.sum())})")
     # the crashed aircraft (the point of this test) and the ones still in the air hold the north-star tolerance. The survivors of a
     # 6-10 m/s touchdown have spent up to ten seconds bouncing on dampers and stick-slip friction regulators (k_i = 400 1/s,
@@ -299,7 +331,7 @@ def test_x2_crash_under_autopilot(fb, oracle):
         def lane_err(xx, cc):
             return np.maximum((np.abs(xx - o["x"]) / x_scale(o["x"])).max(0), (np.abs(cc - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0))
         E = np.stack([lane_err(p["x"], p["cs"])[rolling] for p in pert])
-        conditioning.check_against_envelope(np.maximum(err.max(0), cerr.max(0))[rolling], E, "Xv2 under autopilot, rolling survivors")
+        conditioning.check_against_envelope(np.maximum(err.max(0), cerr.max(0))[rolling], E, label + ", rolling survivors")
     assert np.array_equal(w.s, o["s"])
     w.close()
 
@@ -395,19 +427,23 @@ def test_survivors_sharing_a_wave_with_a_thrower_keep_their_own_launch(fb, oracl
         w.close()
 
 
-def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, oracle):
+@pytest.mark.parametrize("spl,duo,ratio", X2_CASES, ids=X2_IDS)
+def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, oracle, spl, duo, ratio):
     """The same for Cessna172Xv2 through the altitude floor under its autopilot: the bystanders of a replayed wave must keep the ACTUATOR
     positions their launch reached (device rows 27-33, moving under the control laws' commands) — and the brake actuators the steps they
-    completed — not the launch-start values. All 34 rows, the control-law record, s, status word, step and place against the oracle."""
+    completed — not the launch-start values. All 34 rows, the control-law record, s, status word, step and place against the oracle.
+    At seven steps per launch a thrower has had control updates before the evaluation that threw, which its replay must undo (ctl_bak):
+    seen to fail on a library built with -DFB_CTL_BAK_DEFECT, profiles/r07_launch_edge_defects.txt."""
     gains = fb.ctl_gains.ctl_gains_blob()
     K = fb.K
     n = 2048
     rng = np.random.default_rng(101)
     assert geoid(oracle, np.array([0.05]), np.array([1.38]))[0] < -50
     tp = fb.TrimParameters(EAS=rng.uniform(42.0, 55.0, n), h_e=1000.0, ψ_nb=rng.uniform(-np.pi, np.pi, n))
-    w = fb.Cessna172Xv2World(n, gains=gains)
+    with stepper(duo):
+        w = fb.Cessna172Xv2World(n, gains=gains)
     w.set_params(h_terrain=-5000.0)
-    sim = fb.Simulation(w, dt=0.01, Δt=0.02, save_on=False, steps_per_launch=50)
+    sim = fb.Simulation(w, dt=0.01, Δt=0.01 * ratio, save_on=False, steps_per_launch=spl)
     fb.init(sim, tp)
     assert w.trim_success.all()
     perm = ref_to_dev_rows(K)
@@ -429,16 +465,24 @@ def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, ora
     w.u = uu
     X = OracleX(oracle, gains)
     env = oracle.default_env(h_trn=-5000.0)
-    o = X.trim_init(tp.pack(n), fb.TrimState(n), env, 0.02)
+    o = X.trim_init(tp.pack(n), fb.TrimState(n), env, 0.01 * ratio)
     o["status"] = np.zeros(n, np.int32); o["nstep"] = 0
     o["cu"] = np.ascontiguousarray(cu.copy())
     o["x"][perm] = w.x; o["cs"] = w.cs; o["u"] = w.u; o["ui"] = w.ui; o["s"] = w.s
     act0 = o["x"][27:34].copy()
     fb.step(sim, 2.0); w.sync()
-    X.step_term(o, env, 0.01, 2, 200)
+    start = {k: o[k] for k in ("x", "cs", "cu", "u", "ui", "s")}
+
+    def run_oracle():
+        oo = {k: np.array(v, copy=True) for k, v in o.items() if isinstance(v, np.ndarray)}
+        oo["nstep"] = 0
+        X.step_term(oo, env, 0.01, ratio, 200)
+        return oo
+    o = _x2_oracle("floor", ratio, start, run_oracle)
+    label = f"Xv2 through the altitude floor ({spl} steps per launch, {'duo' if duo else 'one-wave'}, Δt = {ratio} dt)"
     st, sto = w.status, o["status"]
     term = sto != 0
-    print("Xv2 through the altitude floor:", int(term.sum()), "of", n, "ended; places", np.unique(o["term_where"][term]))
+    print(label + ":", int(term.sum()), "of", n, "ended; places", np.unique(o["term_where"][term]))
     assert np.array_equal(st, sto) and (sto[term] == K["FB_ST_ALT_RANGE"]).all()
     assert term.sum() >= 400 and (~term).sum() >= 400
     tstep, twhere = w.termination
@@ -449,7 +493,7 @@ def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, ora
     moved = np.abs(o["x"][27:34] - act0).max(0)
     live = ~term
     mixed_waves = sum(1 for k in range(0, n, 64) if term[k:k + 64].any() and live[k:k + 64].any())
-    print(f"Xv2: max scaled error, ended {err[:, term].max():.2e}, survivors {err[:, live].max():.2e} (their actuator rows {err[act_rows][:, live].max():.2e}; "
+    print(f"{label}: max scaled error, ended {err[:, term].max():.2e}, survivors {err[:, live].max():.2e} (their actuator rows {err[act_rows][:, live].max():.2e}; "
           f"actuators moved by up to {moved[live].max():.2f}); {mixed_waves} of {n // 64} waves hold both")
     assert mixed_waves > 20 and (moved[live] > 0.01).mean() > 0.9
     assert err[:, term].max() < 1e-6 and err[:, live].max() < 1e-6
