@@ -8,7 +8,7 @@ typedef FB_REAL real;
 #define FBD __device__ __forceinline__
 // Marks the phase boundaries of one RHS. It used to be a scheduling barrier (__builtin_amdgcn_sched_barrier(0)): while the kernel
 // sat at the register limit, letting the scheduler interleave the phases cost more in spills than the ILP gained. Since the
-// instruction diet of DESIGN.md v9-v15 the registers have slack and the barrier costs 1 %, so it is off; define it to bring it back.
+// instruction diet of DESIGN.md v9-v15 the registers have slack and the barrier costs 1 %, so it is off.
 // FB_STAMP (diagnostic builds only, tools/stamp_profile.py): every fence reads the shader clock and wave 0 of workgroup 0 adds
 // the cycles since the previous fence to g_stamp_acc[k] — a per-phase cycle profile of one wave (MI355X_MICROARCH.md: in-kernel stamps).
 #if defined(FB_STAMP) || defined(FB_TRIM_STAMP)
@@ -28,31 +28,20 @@ __device__ __forceinline__ void fb_stamp(int k) {
     }
     __builtin_amdgcn_sched_barrier(0);
 }
-#define FB_PHASE_FENCE(k) fb_stamp(k)
 #endif
-#ifdef FB_PHASE_MARK   // diagnostic: "; FBPHASE k" comments in the device assembly, for per-phase instruction counts (tools/phase_mix.py)
-#define FB_PHASE_FENCE(k) asm volatile("; FBPHASE %0" ::"n"(k) : "memory")
+#if defined(FB_PHASE_MARK)   // diagnostic: "; FBPHASE k" comments in the device assembly, for per-phase instruction counts (tools/phase_mix.py)
+#define PHASE_FENCE(k) asm volatile("; FBPHASE %0" ::"n"(k) : "memory")
+#elif defined(FB_STAMP)
+#define PHASE_FENCE(k) fb_stamp(k)
+#else
+#define PHASE_FENCE(k) do { } while (0)
 #endif
-#ifndef FB_PHASE_FENCE
-#define FB_PHASE_FENCE(k) do { } while (0)
-#endif
-#ifndef FB_SCALAR_DERIVS
-#define FB_SCALAR_DERIVS 1   // the twenty scalar aero derivatives through scalar loads (0: LDS broadcast reads; same instruction count within 1 %)
-#endif
-#ifndef FB_TWO_LEVEL_SCAN
-#define FB_TWO_LEVEL_SCAN 2   // coarse-then-fine knot scans: 0 never, 1 in the fp32 instance, 2 everywhere (grid_locate)
-#endif
-#ifndef FB_SCALAR_KNOTS_MIN
-#define FB_SCALAR_KNOTS_MIN 3   // tables with at most this many knots are scanned from LDS even when the scalar path is on
-#endif
+constexpr int SCALAR_KNOTS_MIN = 3;   // tables with at most this many knots are scanned from LDS even when the scalar path is on
 // The ground-contact branch of a landing-gear unit is INLINED into the kernels that can meet the ground (k_step_air<.., true>, k_f_ode,
 // k_f_step, k_trim). It used to be out of line, when the airborne and the ground-capable stepper were one kernel and the airborne
 // path could not afford its registers; since the airborne pass is a kernel of its own (GROUND = false: the branch is compiled out)
 // the call only cost the ground-capable pass its stack frame — GroundIn / GroundOut through scratch memory at every contact:
 // 5.1e8 -> 9.4e8 aircraft-steps/s for a batch that sits on the ground (tools/bench_ground.py).
-#ifndef FB_GROUND_ATTR
-#define FB_GROUND_ATTR __forceinline__
-#endif
 
 constexpr real PI = FBL(3.14159265358979323846);
 
@@ -294,30 +283,6 @@ FBD real geoid_height(const Tables& T, v3 n) {
     real la, lo;
     return geoid_height(T, n, la, lo);
 }
-// The same lookup for a caller that evaluates it again and again along one aircraft's path (the wave-pair stepper's role P): the cell's
-// indices and its four samples are kept, and the gather is repeated only when the point has left the cell — an aircraft crosses a 0.25 degree
-// cell every ~9 minutes at 50 m/s, i.e. once in ~50 000 evaluations. Same four floats, same bilinear form: the result is bit for bit
-// geoid_height<true>'s. What it saves is the gather's round trip and, for a fleet spread over the Earth, its L2 misses (a wave's 64 aircraft
-// then touch 64 different cells of the 4.2 MB table: bench_dispersed.py, profiles/r05_dispersed.txt).
-struct GeoidCache { int i, j; float a00, a10, a01, a11; };
-FBD real geoid_height_cached(const Tables& T, v3 n, real& lat, real& lon, GeoidCache& gc) {
-    lat = atan2_step<true>(n.z, sqrt(n.x * n.x + n.y * n.y), T.rk + LDS_ATAN);
-    lon = atan2_step(n.y, n.x, T.rk + LDS_ATAN);
-    const real t2 = lon + 2 * PI;
-    const real lam = t2 >= 2 * PI ? t2 - 2 * PI : t2;
-    const real xi = (lat + PI / 2) * (720 / PI);
-    const real xj = lam * (1440 / (2 * PI));
-    const int i = min(max((int)floor(xi), 0), 719);
-    const int j = min(max((int)floor(xj), 0), 1439);
-    const real wi = xi - i, wj = xj - j;
-    if (i != gc.i || j != gc.j) {
-        const float* p = T.egm96 + i + 721 * j;
-        gc.a00 = p[0]; gc.a10 = p[1]; gc.a01 = p[721]; gc.a11 = p[722];
-        gc.i = i; gc.j = j;
-    }
-    const real a00 = gc.a00, a10 = gc.a10, a01 = gc.a01, a11 = gc.a11;
-    return (1 - wi) * ((1 - wj) * a00 + wj * a01) + wi * ((1 - wj) * a10 + wj * a11);
-}
 // Geoid height of a point (dlat, dlon) [rad] away from the one whose cell is gc — a wheel, a couple of metres from the body
 // origin: the same bilinear interpolant on the same samples, without a second pair of atan2 and (almost always) without a second
 // gather; a point that has crossed into a neighbouring cell fetches that cell's samples.
@@ -404,8 +369,8 @@ struct loc { int i; real w; };
 // SLOT >= 0: the table has a contiguous copy of its first, last and every S-th knot behind the blob (tables.h: LDS_AUX), gb = the blob
 template <int N, bool SCALAR = false, int SLOT = -1>
 FBD loc grid_locate(lds_cptr k, lds_cptr rk, real x, bool flat_lo, bool flat_hi, gk_cptr g = nullptr, gk_cptr gb = nullptr) {
-    if constexpr (SCALAR && N > FB_SCALAR_KNOTS_MIN) {   // (short tables stay in LDS: no scalar-load round trip)
-        constexpr bool TWO_LEVEL = N >= 11 && (FB_TWO_LEVEL_SCAN == 2 || (FB_TWO_LEVEL_SCAN == 1 && sizeof(real) == 4));
+    if constexpr (SCALAR && N > SCALAR_KNOTS_MIN) {   // (short tables stay in LDS: no scalar-load round trip)
+        constexpr bool TWO_LEVEL = N >= 11;   // coarse-then-fine knot scan
         if constexpr (TWO_LEVEL && SLOT >= 0) {   // one scalar load brings the clamps and the coarse knots
             static_assert(2 + (N - 2) / (N >= 20 ? 4 : 3) <= AUX_STRIDE, "coarse knots must fit their slot");
             constexpr int S = N >= 20 ? 4 : 3, G = (N - 2) / S;
@@ -462,15 +427,10 @@ FBD loc range_locate(real a, real b, int n, real x, bool flat) {
 // Table values are read one ds_read_b64 each: left to itself the compiler pairs neighbouring elements into ds_read2_b64, and for
 // ONE wave per SIMD reading lane-dependent (scattered, bank-conflicting) addresses a ds_read2_b64 costs the wave 24-43 issue cycles
 // against 2 x 6-8 for two single reads (tools/microbench/lds.hip: bilinear corners as 2 x read2 +87 cycles, as 4 x read +25).
-// FB_SPLIT_TABLE_READS: the reads go through a volatile pointer, which the load/store optimizer leaves alone.
-#ifndef FB_SPLIT_TABLE_READS
-#define FB_SPLIT_TABLE_READS 1
-#endif
+// So the reads go through a volatile pointer, which the load/store optimizer leaves alone.
 FBD real tab(lds_cptr v, int i) {
-#if FB_SPLIT_TABLE_READS
     // (fp64 only: the fp32 stepper runs two waves per SIMD, where a ds_read2_b32 is the cheaper form — measured 6.72e9 vs 6.46e9)
     if constexpr (sizeof(real) == 8) return *(volatile __attribute__((address_space(3))) const real*)(v + i);
-#endif
     return v[i];
 }
 FBD real lerp1(lds_cptr v, loc l) { return (1 - l.w) * tab(v, l.i) + l.w * tab(v, l.i + 1); }
@@ -654,18 +614,8 @@ struct InputsX {
     FBD real get_brake(int g) const { return pos(g == 0 ? FB_ACT_BRAKE_LEFT : FB_ACT_BRAKE_RIGHT); }
 };
 constexpr real ACT_TAU = FBL(1.0) / 20;  // Actuator1 time constant, c172x.jl:21
-// 1: the ground-capable Cessna172Xv2 steppers reach the three gear units' ground-contact code through CALLS (GroundIn / GroundOut through private memory,
-// caller-saved registers around six calls per evaluation: rounds 2-5, when the inlined branch tripped the spill-placement check); 0 (round 6): inlined
-// like the Cessna172Sv0 instances — 672-732 B of scratch instead of 1 168-1 328, and a batch on the ground steps TWICE as fast (4.31e8 -> 8.95e8
-// aircraft-steps/s, profiles/r06_ab_x2_ground_inline.txt). See docs/design/ground.md, round 6.
-#ifndef FB_X2_GROUND_CALLS
-#define FB_X2_GROUND_CALLS 0
-#endif
 // InputsX with the payload's mass-property sums taken once per launch (see InputsAgg below)
 struct InputsXAgg : InputsX {
-#if FB_X2_GROUND_CALLS
-    typedef void ground_calls_tag;   // (the stepping kernels' Xv2 inputs: ground contact through calls)
-#endif
     static constexpr bool pld_precomputed = true;
     real pld_M, pld_J[6];
     real pld_Mr[3];
@@ -834,16 +784,10 @@ struct GroundOut {
 // them and its crash criterion (> 60 degrees: the strut's GroundCrash, :331-338). FAST (the stepping kernels): the criterion is decided
 // on the cosine — acos is evaluated only for a lane within 1e-7 of cos 60 degrees, where the rounding of acos(x) 180 / pi decides.
 struct GroundCommon { quat q_en; v3 ks_e, ut_e; real ut_ks, alpha_ts; bool tilt_crash; };
-template <bool FAST> __device__ FB_GROUND_ATTR void ground_common(quat q_eb, quat q_en, GroundCommon& c);
+template <bool FAST> __device__ __forceinline__ void ground_common(quat q_eb, quat q_en, GroundCommon& c);
 // FAST = the stepping kernels' forms (see c172_kernels.hpp); !FAST = the reference's operations one by one (f_ode!, the output record)
-template <bool FAST> __device__ FB_GROUND_ATTR void gear_ground_kinematics(const GroundIn& in, GroundOut& o);
-template <bool FAST> __device__ FB_GROUND_ATTR void gear_ground_force(const GroundIn& in, GroundOut& o);
-// out-of-line twins for the instances that cannot afford the inlined branch's registers (Inputs types with ground_calls = true:
-// the Cessna172Xv2 steppers, see step_block() in c172_kernels.hpp)
-template <bool FAST> __device__ __noinline__ void gear_ground_kinematics_call(const GroundIn& in, GroundOut& o);
-template <bool FAST> __device__ __noinline__ void gear_ground_force_call(const GroundIn& in, GroundOut& o);
-template <class In, class = void> struct GroundCalls : std::false_type {};
-template <class In> struct GroundCalls<In, std::void_t<typename In::ground_calls_tag>> : std::true_type {};
+template <bool FAST> __device__ __forceinline__ void gear_ground_kinematics(const GroundIn& in, GroundOut& o);
+template <bool FAST> __device__ __forceinline__ void gear_ground_force(const GroundIn& in, GroundOut& o);
 
 // ---------------------------------------------------------------------------------------------
 // One RHS evaluation. x[27] -> 27 derivatives through emit(); fills aux (for f_step!) and, if Y != nullptr, the output record.
@@ -954,7 +898,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
     constexpr int NC = SinkT::full ? PR_NC : PR_NC_STEP;   // propeller table stride in LDS (see stage_tables)
     auto gkp = [&](int off) -> gk_cptr { return SCALAR_KNOTS ? T.gk + off : nullptr; };
     int32_t st = 0;
-    FB_PHASE_FENCE(0);
+    PHASE_FENCE(0);
     auto YP = [&](int k, real v) { if (WITH_Y) sink.put(k, v); };
     auto YP3 = [&](int k, v3 v) { if (WITH_Y) { sink.put(k, v.x); sink.put(k + 1, v.y); sink.put(k + 2, v.z); } };
     auto YP4 = [&](int k, quat q) { if (WITH_Y) { sink.put(k, q.w); sink.put(k + 1, q.x); sink.put(k + 2, q.y); sink.put(k + 3, q.z); } };
@@ -1021,7 +965,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
     const real N_geoid = geoid_height<FASTM>(T, n_e, lat, lon, gcell);
     const real h_o = h_e - N_geoid;
     if (!(h_o >= H_MIN)) st |= FB_ST_ALT_RANGE;
-    FB_PHASE_FENCE(11);
+    PHASE_FENCE(11);
 
     const v3 v_eb_n = qrot(q_nb, v_eb_b);
     // radii of curvature and ECEF position (geodesy.jl:125-129, 418-428)
@@ -1110,7 +1054,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         YP(FB_Y_KIN + 39, chi_ok ? atan2(-v_eb_n.z, sqrt(v_eb_n.x * v_eb_n.x + v_eb_n.y * v_eb_n.y)) : FBL(0.0));
     }
 
-    FB_PHASE_FENCE(1);
+    PHASE_FENCE(1);
     // ===== air data (atmosphere.jl:269-283, 220-242) =====
     real T_air, p_air;
     real lnp_air;
@@ -1143,7 +1087,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
 
     v3 F_b = {0, 0, 0}, tau_b = {0, 0, 0};  // total external wrench at Ob, body axes
 
-    FB_PHASE_FENCE(2);
+    PHASE_FENCE(2);
     // ===== aerodynamics (c172.jl:307-373, 226-245) =====
     {
         lds_cptr A = T.lds + LDS_AERO;
@@ -1178,9 +1122,9 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         const loc l_be3 = grid_locate<3, SCALAR_KNOTS>(A + AT_CY_BETA_K, RA + AT_CY_BETA_K, be, true, true, gkp(LDS_AERO + AT_CY_BETA_K));
         const loc l_bu = grid_locate<3, SCALAR_KNOTS>(A + AT_UNIT3_K, RA + AT_UNIT3_K, be, true, true, gkp(LDS_AERO + AT_UNIT3_K));
         const loc l_stall = {0, stall ? FBL(1.0) : FBL(0.0)};
-        FB_PHASE_FENCE(12);
+        PHASE_FENCE(12);
         // the twenty scalar derivatives: uniform addresses -> scalar loads when the global blob is available
-        auto S_ = [&](int k) -> real { return (SCALAR_KNOTS && FB_SCALAR_DERIVS) ? T.gk[LDS_AERO + AT_SCALARS + k] : A[AT_SCALARS + k]; };
+        auto S_ = [&](int k) -> real { return SCALAR_KNOTS ? T.gk[LDS_AERO + AT_SCALARS + k] : A[AT_SCALARS + k]; };
         real C_D, C_Y, C_L, C_l, C_m, C_n;
         if constexpr (In::aero_precomputed) {   // (the deflection-only terms come summed with the inputs; same terms, different order of addition)
             const loc l_df4 = ac.l_df4, l_df2 = ac.l_df2;
@@ -1226,7 +1170,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         }
     }
 
-    FB_PHASE_FENCE(3);
+    PHASE_FENCE(3);
     // ===== landing gear: left, right, nose (landinggear.jl:524-537, 228-328, 411-476) =====
     aux.wow = 0;
     aux.crash = 0;
@@ -1249,7 +1193,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
     }
 #pragma unroll
     for (int g = 0; g < 3; g++) {
-        FB_PHASE_FENCE(4);
+        PHASE_FENCE(4);
         v3 r_bs_e = {0, 0, 0}, loc_Ot = {1, 0, 0};
         real he_Ot = 0, dh = 0;
         bool wow = false;
@@ -1282,7 +1226,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
             // ground-only inputs, fetched on demand (c172s.jl:107-110; c172x.jl:139-141)
             gi.steer_in = (g == 2) ? in.get_steering() : FBL(0.0);
             gi.brake_in = (g == 2) ? FBL(0.0) : in.get_brake(g);
-            if constexpr (GroundCalls<In>::value) gear_ground_kinematics_call<GFAST>(gi, go); else gear_ground_kinematics<GFAST>(gi, go);
+            gear_ground_kinematics<GFAST>(gi, go);
             v_xy0 = go.v_xy0; v_xy1 = go.v_xy1;
             st |= go.st;
         }
@@ -1292,7 +1236,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         emit(FB_X_LDG_FRC + 2 * g + 1, pi_ode(frc_kp, frc_ki, frc_kl, -FBL(1.0), FBL(1.0), -v_xy1, x1, out1));
         if constexpr (GROUND) if (wow) {
             gi.frc_out0 = out0; gi.frc_out1 = out1;
-            if constexpr (GroundCalls<In>::value) gear_ground_force_call<GFAST>(gi, go); else gear_ground_force<GFAST>(gi, go);
+            gear_ground_force<GFAST>(gi, go);
             F_b = F_b + go.F_b;
             tau_b = tau_b + go.tau_b;
             aux.wow |= (1 << g);
@@ -1306,14 +1250,14 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         }
     }
 
-    FB_PHASE_FENCE(6);
+    PHASE_FENCE(6);
     // ===== fuel mass (c172.jl:607-616) and total mass properties at Ob (dynamics.jl:328-399; c172.jl:26-44, 542-554, 618-636) =====
     // (they depend on the state alone; the fuel row itself is emitted behind the engine, which supplies the fuel flow)
     const real m_fuel_total = m_res + x[FB_X_FUEL] * (m_full - m_res);
     aux.m_avail = m_fuel_total - m_res;
     YP(FB_Y_FUEL, m_fuel_total);
 
-    FB_PHASE_FENCE(7);
+    PHASE_FENCE(7);
     real M = afm_m, iM = 0;
     v3 r_bc = {0, 0, 0};   // CoM position in body frame
     real J[6] = {0, 0, 0, 0, 0, 0};
@@ -1324,7 +1268,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         Jxx = Jc[0]; Jyy = Jc[1]; Jzz = Jc[2]; Jxy = Jc[3]; Jxz = Jc[4]; Jyz = Jc[5];
     }
 
-    FB_PHASE_FENCE(5);
+    PHASE_FENCE(5);
     // ===== power plant: propeller then engine (piston.jl:575-595; propellers.jl:405-452; piston.jl:314-426) =====
     v3 h_rot = {0, 0, 0};
     real mdot = 0;
@@ -1362,7 +1306,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         F_b = F_b + F_p;
         tau_b = tau_b + tau_pb;
         h_rot = {prop_Jxx * w_prop, FBL(0.0), FBL(0.0)};
-        FB_PHASE_FENCE(9);
+        PHASE_FENCE(9);
 
         // ---- engine ----
         real out_frc, out_idle;
@@ -1408,7 +1352,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
         const loc l_n5s = grid_locate<5, SCALAR_KNOTS>(PT + PT_SFC_N_K, RPT + PT_SFC_N_K, n_eng, false, false, gkp(LDS_PISTON + PT_SFC_N_K));
         const loc l_f = grid_locate<11, SCALAR_KNOTS, AUX_F11>(PT + PT_F_K, RPT + PT_F_K, f_run, true, true, gkp(LDS_PISTON + PT_F_K), T.gk);
         const real pi_ratio = lerp1(PT + PT_PI_RATIO_V, l_f), sfc_ratio = lerp1(PT + PT_SFC_RATIO_V, l_f);
-        FB_PHASE_FENCE(10);
+        PHASE_FENCE(10);
         const real d_wot = lerp2(PT + PT_DELTA_WOT_V, 2, l_n2, range_locate(FBL(0.401), FBL(0.936), 9, mu, false));
         const real pi_std = lerp2(PT + PT_PISTD_V, 13, l_n13, grid_locate<3, SCALAR_KNOTS>(PT + PT_PISTD_MU_K, RPT + PT_PISTD_MU_K, mu, true, true, gkp(LDS_PISTON + PT_PISTD_MU_K)));
         const real pi_wot = lerp2(PT + PT_PIWOT_V, 5, l_n5w, grid_locate<3, SCALAR_KNOTS>(PT + PT_PIWOT_D_K, RPT + PT_PIWOT_D_K, d_wot, true, false, gkp(LDS_PISTON + PT_PIWOT_D_K)));
@@ -1439,7 +1383,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
 
     emit(FB_X_FUEL, -mdot / (m_full - m_res));
 
-    FB_PHASE_FENCE(8);
+    PHASE_FENCE(8);
     // ===== rigid-body dynamics at the CoM (dynamics.jl:443-525) =====
     {
         v3 d_e;
@@ -1478,7 +1422,7 @@ FBD int32_t rhs(const XV& x, int stall, int eng_state, const In& in, const Env& 
             YP3(k + 31, a_ic - gam); YP3(k + 34, wd - cross(w_eb_b, w_ie_b)); YP3(k + 37, g_c_c);
         }
     }
-    FB_PHASE_FENCE(20);
+    PHASE_FENCE(20);
     return st;
 }
 

@@ -32,15 +32,6 @@
 //   * the control and flag words of an evaluation are role D's, written before its point T, which role P waits for at the top of its loop
 //     (role D has waited for W of the evaluation before, so role P has long read the previous ones).
 #pragma once
-// 1: role P keeps its aircraft's EGM96 cell (indices + four samples, six registers of the ~130 it has to spare) across the evaluations of a launch
-// and gathers again only when the aircraft has left the cell: geoid_height_cached (c172_device_impl.inc). 0 (shipped): gather at every evaluation.
-// Measured, round 5 (profiles/r05_ab_geoid_cache.txt, same box, alternating): a fleet spread over the sphere 14.21-14.24 -> 14.01-14.02 ms per
-// launch — the whole cost of dispersion (1.7 %) — but the benchmark batch, which sits in ONE cell (every gather a wave-wide broadcast that
-// hits the L2), 13.96 -> 14.03 ms: the compare-and-branch per evaluation costs the pair more issue slots than the four broadcast loads did.
-// The headline configuration decides; a user whose fleet covers the globe builds with -DFB_DUO_GEOID_CACHE=1.
-#ifndef FB_DUO_GEOID_CACHE
-#define FB_DUO_GEOID_CACHE 0
-#endif
 #include "c172_device.hpp"
 
 namespace fbd {
@@ -132,11 +123,9 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         emit.xpub(DUO_PT_R);   // ----- point R: state rows read (role D may rewrite the kinematics rows; this wave's previous evaluation is complete) -----
         if constexpr (X) __builtin_amdgcn_s_setprio(0);   // (Cessna172Xv2: this role ran ahead of role D from the top of its loop to here, see k_step_duo)
         double lat, lon;
-        // (the Cessna172Sv0 instances: role P has the six registers; in the Cessna172Xv2 ones, where it also carries the actuators, they spill)
-        double N_geoid;
-        if constexpr (FB_DUO_GEOID_CACHE && !Emit::x2) N_geoid = geoid_height_cached(T, n_e, lat, lon, *emit.gcache);
-        else N_geoid = geoid_height<true>(T, n_e, lat, lon);
-        const double h_o = h_e - N_geoid;
+        // (gathered at every evaluation: a per-lane cache of the EGM96 cell gains 1.5 % for a fleet spread over the sphere and loses 0.5 % on a batch
+        // that sits in one cell, profiles/r05_ab_geoid_cache.txt; the removed code is profiles/r07_duo_geoid_cache.patch)
+        const double h_o = h_e - geoid_height<true>(T, n_e, lat, lon);
         if (!(h_o >= H_MIN)) st |= FB_ST_ALT_RANGE;
         if constexpr (X) {
             if (emit.tap) {   // kinematics.y.ϕ_λ as the guidance reads it (rhs(): the states themselves in the NED mechanisation)
@@ -214,10 +203,8 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
 DUO_MARK(1, 6);   // engine head done
         // behind W role P has the longer way to go (the rest of the engine: ~400 instructions against role D's ~110 once it has the wrench): it
         // goes ahead of D in issue priority until its evaluation ends (profiles/r03_ab_prio.txt)
-#ifndef FB_DUO_P_TAIL_PRIO
-#define FB_DUO_P_TAIL_PRIO 3
-#endif
-        __builtin_amdgcn_s_setprio(FB_DUO_P_TAIL_PRIO);
+        constexpr int DUO_P_TAIL_PRIO = 3;
+        __builtin_amdgcn_s_setprio(DUO_P_TAIL_PRIO);
         const double k_f = rsqrt(rho * (1 / isa::rho_std));
         const bool mix_auto = in.ui & FB_UI_MIXTURE_AUTO;
         const double f_run = mix_auto ? f_lean + mixture * (f_rich - f_lean) : k_f * (f_rich * (0.5 * (mixture + 1)));
@@ -434,7 +421,7 @@ DUO_MARK(1, 6);   // engine head done
         const double p_nd = w_wb_b.x * b * i2V, q_nd = w_wb_b.y * c * i2V, r_nd = w_wb_b.z * b * i2V;
         const double dh_nd = (h_o - env.h_trn) / b;
         const loc l_ge = grid_locate<13, true, AUX_GE>(A + AT_GE_K, RA + AT_GE_K, dh_nd, true, true, gkp(LDS_AERO + AT_GE_K), T.gk);
-        auto S_ = [&](int k) -> double { return FB_SCALAR_DERIVS ? T.gk[LDS_AERO + AT_SCALARS + k] : A[AT_SCALARS + k]; };
+        auto S_ = [&](int k) -> double { return T.gk[LDS_AERO + AT_SCALARS + k]; };
         if constexpr (X) {   // InputsAgg::sum_aero's expressions for the sums that are linear in the deflections
             ac.cy_in = S_(AS_CY_DR) * x2_dr + S_(AS_CY_DA) * x2_da;
             ac.cl_in = S_(AS_CL_DE) * x2_de;

@@ -35,7 +35,7 @@ namespace fbd {
 //   * the skid azimuth by the stepping kernels' table atan2; reciprocal square roots where the reference divides by a square root;
 //   * F_b = N (q_sc f_c) from the rotation already made for N, instead of rotating N f_c again.
 template <bool FAST>
-__device__ FB_GROUND_ATTR void ground_common(quat q_eb, quat q_en, GroundCommon& c) {
+__device__ __forceinline__ void ground_common(quat q_eb, quat q_en, GroundCommon& c) {
     c.q_en = q_en;
     if constexpr (FAST) {
         // qrot(q, (0,0,1)) = (2 (q_y q_w + q_z q_x), 2 (q_z q_y - q_x q_w), 1 - 2 (q_x^2 + q_y^2)), term by term as the generic form makes them
@@ -61,7 +61,7 @@ __device__ FB_GROUND_ATTR void ground_common(quat q_eb, quat q_en, GroundCommon&
     }
 }
 template <bool FAST>
-__device__ FB_GROUND_ATTR void gear_ground_kinematics(const GroundIn& in, GroundOut& o) {
+__device__ __forceinline__ void gear_ground_kinematics(const GroundIn& in, GroundOut& o) {
     using namespace c172;
     const int g = in.g;
     const v3 r_bs_b = {ldg_r[g][0], ldg_r[g][1], ldg_r[g][2]};
@@ -160,7 +160,7 @@ __device__ FB_GROUND_ATTR void gear_ground_kinematics(const GroundIn& in, Ground
 }
 
 template <bool FAST>
-__device__ FB_GROUND_ATTR void gear_ground_force(const GroundIn& in, GroundOut& o) {
+__device__ __forceinline__ void gear_ground_force(const GroundIn& in, GroundOut& o) {
     const double nv = sqrt(o.v_xy0 * o.v_xy0 + o.v_xy1 * o.v_xy1);
     auto mu = [&](double mu_s, double mu_d) {
         const double k = fmin(fmax((nv - 0.005) / (0.01 - 0.005), 0.0), 1.0);
@@ -190,9 +190,6 @@ __device__ FB_GROUND_ATTR void gear_ground_force(const GroundIn& in, GroundOut& 
     o.F_b = F_b;
     o.tau_b = cross(o.r_bc_b, F_b);
 }
-
-template <bool FAST> __device__ __noinline__ void gear_ground_kinematics_call(const GroundIn& in, GroundOut& o) { gear_ground_kinematics<FAST>(in, o); }
-template <bool FAST> __device__ __noinline__ void gear_ground_force_call(const GroundIn& in, GroundOut& o) { gear_ground_force<FAST>(in, o); }
 
 // ---- kernel arguments -----------------------------------------------------------------------
 struct KArgs {
@@ -303,20 +300,12 @@ FBD void load_inputs(const KArgs& a, int64_t i, Inputs& in) {
 // another c, and then the derivative at x_{n+1} that one launch carries over to the next (k_step_air<X>'s k1, evaluated ahead of the control update with
 // the OLD commands) and the one a launch evaluates for itself (behind it, with the NEW ones) are not the same numbers: a run cut into launches
 // differently — a host callback after every step against a scenario table on the device — differed in the last place
-// (tests/test_gpu_scenarios.py compares the two bit for bit). FB_ACT_STAGE_FORM: 2 this form; 1 the old one with the first stage selected
-// (+0.9 % on the Cessna172Xv2 launch, profiles/r06_ab_stage0.txt); 0 the old one (rounds 3-5).
-#ifndef FB_ACT_STAGE_FORM
-#define FB_ACT_STAGE_FORM 2
-#endif
-FBD double act_stage_mc(int stage, double z) {   // 1 - ms (form 2), ms (forms 0, 1)
-    if constexpr (FB_ACT_STAGE_FORM == 2) return stage == 0 ? 0.0 : (stage == 1 ? z / 2 : (stage == 2 ? z / 2 - z * z / 4 : z - z * z / 2 + z * z * z / 4));
-    else return stage == 0 ? 1.0 : (stage == 1 ? 1 - z / 2 : (stage == 2 ? 1 - z / 2 + z * z / 4 : 1 - z + z * z / 2 - z * z * z / 4));
+// (tests/test_gpu_scenarios.py compares the two bit for bit; the old form with the first stage selected costs +0.9 % on the Cessna172Xv2 launch,
+// profiles/r06_ab_stage0.txt).
+FBD double act_stage_mc(int stage, double z) {   // 1 - ms
+    return stage == 0 ? 0.0 : (stage == 1 ? z / 2 : (stage == 2 ? z / 2 - z * z / 4 : z - z * z / 2 + z * z * z / 4));
 }
-FBD double act_stage_pos(double x_n, double c, double mc, [[maybe_unused]] bool first_stage) {
-    if constexpr (FB_ACT_STAGE_FORM == 2) return __builtin_fma(c - x_n, mc, x_n);
-    else if constexpr (FB_ACT_STAGE_FORM == 1) return first_stage ? x_n : c + (x_n - c) * mc;
-    else return c + (x_n - c) * mc;
-}
+FBD double act_stage_pos(double x_n, double c, double mc) { return __builtin_fma(c - x_n, mc, x_n); }
 // (in two parts — the row as it stands in memory, and its saturation — for callers that want all seven loads in flight before the first clamp)
 FBD double x2_command_row(const KArgs& a, int64_t i, int k) {
     const int64_t n = a.n;
@@ -334,11 +323,6 @@ FBD double x2_command_sat(int k, double v) { return clampd(v, (k == FB_ACT_AILER
 FBD double x2_command(const KArgs& a, int64_t i, int k) { return x2_command_sat(k, x2_command_row(a, i, k)); }
 // dst[k n + i] = src[k n + i], k < ROWS, G rows at a time: G loads in flight, then G stores. (Row by row — a load, a wait, a store, the next
 // load behind the store it may alias — the launch-start copy of the control-law record was 94 dependent memory round trips per workgroup.)
-// (k_step_duo's two copies: rows per batch, and a diagnostic switch — FB_X2_BAK = 0 leaves the copies out, which is WRONG for a lane that is handed
-// over behind a control update and only measures what they cost)
-#ifndef FB_X2_BAK
-#define FB_X2_BAK 1
-#endif
 // Launches of up to FB_CTL_BAK_SKIP steps take neither the launch-start copy of the control-law record nor its way back: one step only (the
 // argument is at k_step_air's copy). -DFB_CTL_BAK_DEFECT rebuilds the defect this guards against — no copy up to seven steps, where a lane is
 // handed over behind control updates of its own launch — so that the tests can be seen to fail on it: tests/test_gpu_launch_edges.py,
@@ -349,12 +333,8 @@ FBD double x2_command(const KArgs& a, int64_t i, int k) { return x2_command_sat(
 #else
 #define FB_CTL_BAK_SKIP 1
 #endif
-#ifndef FB_X2_BAK_G_CS
-#define FB_X2_BAK_G_CS 11
-#endif
-#ifndef FB_X2_BAK_G_CU
-#define FB_X2_BAK_G_CU 14
-#endif
+constexpr int CTL_BAK_G_CS = 11, CTL_BAK_G_CU = 14;   // rows per batch of the two copies (cs, cu)
+static_assert(FB_NCS % CTL_BAK_G_CS == 0 && FB_NCU % CTL_BAK_G_CU == 0, "batch sizes of the record copies");
 template <int ROWS, int G>
 __device__ __forceinline__ void copy_rows_batched(double* dst, const double* src, int64_t n, int64_t i) {
     static_assert(ROWS % G == 0, "");
@@ -411,13 +391,10 @@ template <class P> FBD P* uni(P* p) { return (P*)(uintptr_t)uni((int64_t)(uintpt
 struct CtlOut { double cmd[4]; };   // throttle, aileron, elevator, rudder, as x2_command() would read them back
 // Inlined into k_step_air<KIN, true, GROUND> since round 4: out of line (rounds 2-3, "the call costs 4.9 k cycles") it was a callee that saved and
 // restored the callee-saved registers it used through scratch; inlined, the one-wave airborne pass runs 14.05 -> 12.8 ms per launch of 524 288
-// (profiles/r04_x2_inline_ab.txt, second table). -DFB_X2_PERIODIC_ATTR=__noinline__ builds the old form.
-#ifndef FB_X2_PERIODIC_ATTR
-#define FB_X2_PERIODIC_ATTR __forceinline__
-#endif
-__device__ FB_X2_PERIODIC_ATTR CtlOut x2_periodic(const double* a_cu, double* a_cs, const double* a_gains, int64_t a_n, double a_dT, uint32_t o01, uint32_t o23,
+// (profiles/r04_x2_inline_ab.txt, second table).
+__device__ __forceinline__ CtlOut x2_periodic(const double* a_cu, double* a_cs, const double* a_gains, int64_t a_n, double a_dT, uint32_t o01, uint32_t o23,
                                            uint32_t o45, uint32_t o67, uint32_t o89, uint32_t tsg, int64_t i, const CtlIn& v) {
-    FB_X2_STAMP(21);
+    X2_STAMP(21);
     const double* cu = uni(a_cu); double* cs = uni(a_cs); const double* gains = uni(a_gains);
     const int64_t n = uni(a_n);
     const double dT = uni(a_dT);
@@ -443,26 +420,23 @@ __device__ FB_X2_PERIODIC_ATTR CtlOut x2_periodic(const double* a_cu, double* a_
         for (int k = 0; k < FB_NCS; k++) ls[k] = c0[(int64_t)k * n];
     }
     const CtlMemCachedT<gptr> M = {(gptr)(uintptr_t)cu + i, (gptr)(uintptr_t)cs + i, n, lu, ls};
-    FB_X2_STAMP(22);
+    X2_STAMP(22);
     gdc_update(M, v);
-    FB_X2_STAMP(23);
+    X2_STAMP(23);
     const CtlTabT<gcptr> tab = ctl_tab((gcptr)(uintptr_t)gains, off, v.EAS, v.h_e);
     ctl_lon(tab, M, dT, v, (int)M.U(FB_CU_LON_MODE_REQ));
-    FB_X2_STAMP(24);
+    X2_STAMP(24);
     // (fetching the lateral gains ahead of the longitudinal channel, to hide their gather behind its dependent chains, holds 40 more
     // values across it: 460 registers in this function, and the calling kernel's allocation pays — 14.2 -> 15.0 ms per launch)
     const int lat_req = (int)M.U(FB_CU_LAT_MODE_REQ);
     ctl_lat(tab, M, dT, v, lat_req, ctl_lat_gains(tab, v, lat_req));
-    FB_X2_STAMP(25);
+    X2_STAMP(25);
     return {{clampd(M.S(FB_CS_THROTTLE_CMD), 0, 1), clampd(M.S(FB_CS_AILERON_CMD), -1, 1), clampd(M.S(FB_CS_ELEVATOR_CMD), -1, 1), clampd(M.S(FB_CS_RUDDER_CMD), -1, 1)}};
 }
 
-// FB_VERB_FAST: the single-call verbs with f_ode! in the stepping kernels' form (their atan2 / log / sincos, knot scans through scalar loads) instead
-// of the form with the library's functions. Measured, no gain (k_f_ode 0.404 against 0.405-0.413 ms per 1 048 576 aircraft: it is bound by its
-// 1.4 KB of output per aircraft, 3.6 TB/s of stores), so the verbs keep the library form.
-#ifndef FB_VERB_FAST
-#define FB_VERB_FAST false
-#endif
+// The single-call verbs evaluate f_ode! in the form with the library's functions (rhs<KIN, GROUND>: SCALAR_KNOTS = false), not in the stepping kernels'
+// form (their atan2 / log / sincos, knot scans through scalar loads): measured, no gain (k_f_ode 0.404 against 0.405-0.413 ms per 1 048 576 aircraft:
+// it is bound by its 1.4 KB of output per aircraft, 3.6 TB/s of stores).
 // f_ode!(world): xdot (optional) and the output record y
 template <bool X, int KIN>
 __global__ __launch_bounds__(256) void k_f_ode(KArgs a, double* xdot, double* y) {
@@ -481,13 +455,13 @@ __global__ __launch_bounds__(256) void k_f_ode(KArgs a, double* xdot, double* y)
     int32_t st;
     if constexpr (X) {
         const InputsX in = {&x[X2_ACT], a.u + i, a.n, a.ui[i]};
-        st = rhs<KIN, true, FB_VERB_FAST>(x, a.s[i], a.s[a.n + i], in, env_any(a, i), T, emit, aux, PanelSink{y + i, a.n});
+        st = rhs<KIN, true>(x, a.s[i], a.s[a.n + i], in, env_any(a, i), T, emit, aux, PanelSink{y + i, a.n});
 #pragma unroll
         for (int k = 0; k < FB_NACT; k++) xd[X2_ACT + k] = 1 / ACT_TAU * (x2_command(a, i, k) - x[X2_ACT + k]);   // Actuator1.f_ode!, c172x.jl:39-52
     } else {
         Inputs in;
         load_inputs(a, i, in);
-        st = rhs<KIN, true, FB_VERB_FAST>(x, a.s[i], a.s[a.n + i], in, env_any(a, i), T, emit, aux, PanelSink{y + i, a.n});
+        st = rhs<KIN, true>(x, a.s[i], a.s[a.n + i], in, env_any(a, i), T, emit, aux, PanelSink{y + i, a.n});
     }
     if (xdot) {
 #pragma unroll
@@ -516,12 +490,12 @@ __global__ __launch_bounds__(256) void k_f_step(KArgs a) {
     int32_t st;
     if constexpr (X) {
         const InputsX in = {&x[X2_ACT], a.u + i, a.n, a.ui[i]};
-        st = rhs<KIN, true, FB_VERB_FAST>(x, stall, eng, in, env_any(a, i), T, emit, aux, NoSink{});
+        st = rhs<KIN, true>(x, stall, eng, in, env_any(a, i), T, emit, aux, NoSink{});
         f_step<KIN>(x, stall, eng, in, aux, st);
     } else {
         Inputs in;
         load_inputs(a, i, in);
-        st = rhs<KIN, true, FB_VERB_FAST>(x, stall, eng, in, env_any(a, i), T, emit, aux, NoSink{});
+        st = rhs<KIN, true>(x, stall, eng, in, env_any(a, i), T, emit, aux, NoSink{});
         f_step<KIN>(x, stall, eng, in, aux, st);
     }
 #pragma unroll
@@ -550,9 +524,6 @@ __global__ __launch_bounds__(256) void k_f_step(KArgs a) {
 // identically zero (reset by f_step! whenever a wheel is off the ground, zero derivative at zero) so they need no rows —
 // a lane that arrives with a non-zero one is handed to the ground-capable pass — and the eleven per-lane inputs fit in the
 // registers the panels freed. 3 x 21 rows x 2 KB + 22 KB of tables = 151 KB.
-#ifndef FB_AIR_SCALAR_KNOTS
-#define FB_AIR_SCALAR_KNOTS true
-#endif
 // GROUND = true is the same kernel for the lanes the airborne pass hands over (second pass of a launch): all 27 rows and the
 // ground-contact branch compiled in (see step_block() for its workgroup size).
 template <int STRIDE, bool GROUND = false>
@@ -626,19 +597,12 @@ struct AirEmit {
 // see __graft_entry__.py) the 256-lane form tripped that check and every ground instance ran 192 lanes (7.9e8 aircraft-steps/s on a
 // batch sitting on the ground); without it the Sv0 instances have registers to spare and no spill code at all. The Cessna172Xv2 instances
 // stayed at 192 lanes (three panels in LDS: three one-wave SIMDs of four) with the gear units' ground contact behind calls until round 6:
-// inlined (FB_X2_GROUND_CALLS = 0) and at 256 lanes they pass the check, and a batch on the ground steps 2.9 x as fast
+// inlined (the calls: profiles/r07_x2_ground_calls.patch) and at 256 lanes they pass the check, and a batch on the ground steps 2.9 x as fast
 // (4.31e8 -> 8.95e8 -> 1.24e9 aircraft-steps/s, profiles/r06_ab_x2_ground_inline.txt).
-#ifndef FB_GROUND_BLOCK_X
-#define FB_GROUND_BLOCK_X 256
-#endif
-#ifndef FB_GROUND_BLOCK_S
-#define FB_GROUND_BLOCK_S 256
-#endif
-template <bool X, bool GROUND> constexpr int step_block() { return GROUND ? (X ? FB_GROUND_BLOCK_X : FB_GROUND_BLOCK_S) : STEP_BLOCK; }
-template <bool X, bool GROUND> constexpr bool step_acc_in_regs() { return GROUND && step_block<X, GROUND>() > 192; }
-#ifndef FB_STEP_ATTR
-#define FB_STEP_ATTR
-#endif
+constexpr int GROUND_BLOCK_X = 256, GROUND_BLOCK_S = 256;
+template <bool X, bool GROUND> constexpr int step_block() { return GROUND ? (X ? GROUND_BLOCK_X : GROUND_BLOCK_S) : STEP_BLOCK; }
+template <bool X, bool GROUND> constexpr bool step_acc_in_regs() { return GROUND; }
+static_assert(GROUND_BLOCK_X > 192 && GROUND_BLOCK_S > 192, "above 192 lanes three 27-row panels do not fit the LDS: the ground-capable instances keep the stage sum in registers");
 // diagnostic builds (-DFB_STAMP, tools/stamp_ground_launch.py): where a launch of the ground-capable Cessna172Xv2 pass spends its cycles outside the
 // evaluations — slots 13 entry, 14 tables staged, 15 x_n in LDS, 30 loop entered (inputs, commands, the carried k1), 31 state written back
 #ifdef FB_STAMP
@@ -647,7 +611,7 @@ template <bool X, bool GROUND> constexpr bool step_acc_in_regs() { return GROUND
 #define FB_LAUNCH_STAMP(k) do { } while (0)
 #endif
 template <int KIN, bool X = false, bool GROUND = false, bool PERENV = false>
-__global__ __launch_bounds__((step_block<X, GROUND>())) FB_STEP_ATTR void k_step_air(KArgs a, int nsteps) {
+__global__ __launch_bounds__((step_block<X, GROUND>())) void k_step_air(KArgs a, int nsteps) {
     constexpr int B = step_block<X, GROUND>(), NR = GROUND ? (int)FB_NX : FB_NX - 6;
     constexpr bool ACC_REGS = step_acc_in_regs<X, GROUND>();
     using SV = StateLds<B, GROUND>;
@@ -739,11 +703,11 @@ restart:
         // and the one-step cases of tests/test_gpu_termination.py's Cessna172Xv2 tests: hand-overs and throws at 1, 7 and 50 steps per launch.)
         if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP && mine) {
             if (!replaying) {
-                copy_rows_batched<FB_NCS, 11>(a.ctl_bak, a.cs, a.n, il);
-                copy_rows_batched<FB_NCU, 14>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, il);
+                copy_rows_batched<FB_NCS, CTL_BAK_G_CS>(a.ctl_bak, a.cs, a.n, il);
+                copy_rows_batched<FB_NCU, CTL_BAK_G_CU>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, il);
             } else {
-                copy_rows_batched<FB_NCS, 11>(a.cs, a.ctl_bak, a.n, il);
-                copy_rows_batched<FB_NCU, 14>(const_cast<double*>(a.cu), a.ctl_bak + (int64_t)FB_NCS * a.n, a.n, il);
+                copy_rows_batched<FB_NCS, CTL_BAK_G_CS>(a.cs, a.ctl_bak, a.n, il);
+                copy_rows_batched<FB_NCU, CTL_BAK_G_CU>(const_cast<double*>(a.cu), a.ctl_bak + (int64_t)FB_NCS * a.n, a.n, il);
             }
         }
     }
@@ -841,7 +805,7 @@ restart:
                     if constexpr (X) {
                         const double ms = act_stage_mc(stage, z);
 #pragma unroll
-                        for (int k = 0; k < NAL; k++) xa[k] = act_stage_pos(xa[k], ca[k], ms, false);   // (the argument the evaluation was given: the same expression)
+                        for (int k = 0; k < NAL; k++) xa[k] = act_stage_pos(xa[k], ca[k], ms);   // (the argument the evaluation was given: the same expression)
                     }
                 }
                 if constexpr (X) { if (a.k1) a.k1_valid[i] = 0; }
@@ -854,7 +818,7 @@ restart:
             if constexpr (X) {
                 const double ms = act_stage_mc(stage, z);
 #pragma unroll
-                for (int k = 0; k < NAL; k++) xa_s[k] = act_stage_pos(xa[k], ca[k], ms, stage == 0);
+                for (int k = 0; k < NAL; k++) xa_s[k] = act_stage_pos(xa[k], ca[k], ms);
                 if constexpr (!GROUND) { xa_s[FB_ACT_BRAKE_LEFT] = 0; xa_s[FB_ACT_BRAKE_RIGHT] = 0; }   // (never read in the air)
                 inl.xa = xa_s;
                 inl.u_glob = in.u_glob + lds_off;
@@ -867,9 +831,9 @@ restart:
                 // the evaluation at x_{n+1} of a step that closes a control period is the "last f_ode!" whose outputs the control
                 // laws read: the partial sink is switched on for it (ONE instance of rhs() in the loop: CtlSinkOpt)
                 tap.on = tap_now;
-                bits = rhs<KIN, GROUND, FB_AIR_SCALAR_KNOTS>(xv, stall, eng, inl, env, T, emit, aux, tap);
+                bits = rhs<KIN, GROUND, true>(xv, stall, eng, inl, env, T, emit, aux, tap);
             } else
-                bits = rhs<KIN, GROUND, FB_AIR_SCALAR_KNOTS>(xv, stall, eng, inl, env, T, emit, aux, NoSink{});
+                bits = rhs<KIN, GROUND, true>(xv, stall, eng, inl, env, T, emit, aux, NoSink{});
             if constexpr (!GROUND) {
                 // within reach of the ground, or an exception: nothing is committed for this lane, the ground-capable pass takes it over
                 if (bits != 0) { handoff = true; alive = false; run = false; bits = 0; }
@@ -932,7 +896,7 @@ restart:
                         auto pk = [&](int k) { return (uint32_t)a.ctl_off.off[k] | ((uint32_t)a.ctl_off.off[k + 1] << 16); };
                         const CtlOut co = x2_periodic(a.cu, a.cs, a.gains, a.n, a.ctl_dT, pk(0), pk(2), pk(4), pk(6), pk(8),
                                                       (uint32_t)a.ctl_off.total | ((uint32_t)a.ctl_off.same_grid << 16), i, v);
-                        FB_X2_STAMP(26);
+                        X2_STAMP(26);
                         static_assert(FB_ACT_THROTTLE == 0 && FB_ACT_AILERON == 1 && FB_ACT_ELEVATOR == 2 && FB_ACT_RUDDER == 3, "CtlOut order");
 #pragma unroll
                         for (int k = 0; k < 4; k++) ca[k] = co.cmd[k];   // the commands in force from the next stage on (flaps and brakes are inputs: unchanged)
@@ -1121,24 +1085,9 @@ template <int HALF> __device__ __forceinline__ void half_stamp(int k) {
 // Inlined into k_step_duo<KIN,true>: as an out-of-line callee each half saved and restored the callee-saved VGPR groups it used through scratch
 // (~170 stores + 170 loads per pair-update, ~9 GB each way per launch); inlined the kernel holds 249 registers and has no scratch frame at all.
 // Same-box alternating A/B (profiles/r04_x2_inline_ab.txt): ratio 2 10.90 -> 10.37 ms, ratio 1 13.9 -> 12.5 ms, ratio 50 8.25 -> 8.35 ms.
-#ifndef FB_X2_HALF_ATTR
-#define FB_X2_HALF_ATTR __forceinline__
-#endif
-// FB_X2_SPLIT_PITCH = 1 (round 6; OFF: measured, no gain): the longitudinal half is the long one of an update — 27 k cycles
-// against the lateral half's 14 k, profiles/r05_x2_half_stamps.txt — so its pitch-axis outer loops (c2θ PID, θ -> q, q2e integrator + PID: 5 k of its
-// 8 k of outer loops) run on the LATERAL half's wave, ahead of the lateral laws, and their elevator reference reaches the te2te LQR — restructured so
-// that everything that does not need it comes first (lqr_run_g_late) — through an LDS slot and a fifth point Z of the pair's counters. Correct
-// (26 GPU tests, 2.5e-12 against the oracle) and NOT faster: 9.96-9.99 ms per launch against 9.84-9.86, at every combination of issue priorities
-// (profiles/r06_ab_x2_split_pitch.txt). The two halves share one SIMD's issue slots: an update costs what the pair's ~4 900 instructions cost,
-// whichever wave issues them — the lateral wave's "waiting" was never idle time that work could be moved into. Kept for the record.
-#ifndef FB_X2_SPLIT_PITCH
-#define FB_X2_SPLIT_PITCH 0
-#endif
-// hand: how the pitch-axis outer loops' elevator reference crosses from the lateral half's wave to the longitudinal half's (k_step_duo: an LDS
-// slot and the pair's counters): hand.put(v) in the lateral half — store, then publish —, hand.get() in the longitudinal one — wait, then load
-template <int HALF, class Hand>
-__device__ FB_X2_HALF_ATTR Ctl2 x2_periodic_half(const double* a_cu, double* a_cs, const double* a_gains, const double* a_tap, int64_t a_n, double a_dT, uint32_t o01,
-                                              uint32_t o23, uint32_t o45, uint32_t o67, uint32_t o89, uint32_t tsg, int64_t i, double h_e, lds_cptr xs, const Hand& hand) {
+template <int HALF>
+__device__ __forceinline__ Ctl2 x2_periodic_half(const double* a_cu, double* a_cs, const double* a_gains, const double* a_tap, int64_t a_n, double a_dT, uint32_t o01,
+                                              uint32_t o23, uint32_t o45, uint32_t o67, uint32_t o89, uint32_t tsg, int64_t i, double h_e, lds_cptr xs) {
     constexpr int B = 256;   // (= DUO_B, defined below)
     using SV = StateLds<B, false>;
     FB_HALF_STAMP(HALF, -1);
@@ -1163,10 +1112,6 @@ __device__ FB_X2_HALF_ATTR Ctl2 x2_periodic_half(const double* a_cu, double* a_c
             v.chi = TAP(DUO_TAP_CHI); v.beta = TAP(DUO_TAP_BETA);
             v.theta = 0; v.clm = 0;
             v.w_wb_b = {TAP(DUO_TAP_WX), 0.0, 0.0};
-            if constexpr (FB_X2_SPLIT_PITCH != 0) {   // (+ pitch and yaw rate: what the pitch-axis outer loops read, ctl_lon_pitch_half)
-                v.theta = TAP(DUO_TAP_THETA); v.clm = -TAP(DUO_TAP_VD);
-                v.w_wb_b = {TAP(DUO_TAP_WX), TAP(DUO_TAP_WY), TAP(DUO_TAP_WZ)};
-            }
             v.pos[1] = TAP(DUO_TAP_POS + 1); v.pos[3] = TAP(DUO_TAP_POS + 3); v.cmd[1] = TAP(DUO_TAP_CMD + 1); v.cmd[3] = TAP(DUO_TAP_CMD + 3);
             v.pos[0] = v.pos[2] = v.cmd[0] = v.cmd[2] = 0; v.alpha = 0;
         }
@@ -1184,16 +1129,10 @@ __device__ FB_X2_HALF_ATTR Ctl2 x2_periodic_half(const double* a_cu, double* a_c
     FB_HALF_STAMP(HALF, HALF == CTL_HALF_LON ? 23 : 17);   // guidance
     const CtlTabT<gcptr> tab = ctl_tab((gcptr)(uintptr_t)A.gains, A.off, v.EAS, v.h_e);
     if constexpr (HALF == CTL_HALF_LON) {
-        // (FB_X2_SPLIT_PITCH: the pitch-axis outer loops run on the partner wave; their elevator reference arrives inside the te2te LQR's run)
-        ctl_lon<true, FB_X2_SPLIT_PITCH != 0>(tab, M, A.dT, v, (int)M.U(FB_CU_LON_MODE_REQ), [&]() { return hand.get(); });
+        ctl_lon<true>(tab, M, A.dT, v, (int)M.U(FB_CU_LON_MODE_REQ));
         FB_HALF_STAMP(HALF, 24);   // (behind ctl_lon's fence 29: the LQR run and the stores)
         return {clampd(M.S(FB_CS_THROTTLE_CMD), 0, 1), clampd(M.S(FB_CS_ELEVATOR_CMD), -1, 1)};
     } else {
-        if constexpr (FB_X2_SPLIT_PITCH != 0) {
-            // first the longitudinal channel's pitch-axis outer loops (c2θ, θ -> q, q2e), whose result the partner wave's te2te LQR waits for
-            hand.put(ctl_lon_pitch_half(tab, M, A.dT, v, (int)M.U(FB_CU_LON_MODE_REQ)));
-            FB_HALF_STAMP(HALF, 18);   // pitch-axis outer loops, reference handed over
-        }
         const int lat_req = (int)M.U(FB_CU_LAT_MODE_REQ);
         LatGains G;   // (not read: the gains are taken where they are used)
         G.P = {0, 0, 0, 0};
@@ -1223,28 +1162,22 @@ __device__ FB_X2_HALF_ATTR Ctl2 x2_periodic_half(const double* a_cu, double* a_c
 // the one-wave stepper and the oracle.
 constexpr int DUO_B = 256;
 constexpr int DUO_NP = 4, DUO_ND = 17;   // state rows per role
-#ifndef FB_DUO_NPL
-#define FB_DUO_NPL 0
-#endif
-// role P's own x_n rows (fuel, engine: nobody else writes them) in registers, refreshed from the panel at every stage 0: its emits — the
-// last thing of its evaluation, behind role D's point X — then start without an LDS round trip (the Cessna172Sv0 instances: the Xv2 ones spill with it)
-#ifndef FB_DUO_P_XN_REGS
-#define FB_DUO_P_XN_REGS 1
-#endif
-constexpr int DUO_NPL = FB_DUO_NPL;   // how many of role P's four stage sums live in LDS (what is left of the 160 KB)
+// how many of role P's four stage sums live in LDS: none, all four in registers. (Kept as a constant with the code for other values: with the
+// zero-trip loops and the comparisons against it removed, the compiler schedules every k_step_duo instance differently — same registers and LDS,
+// other instruction order — and an instruction order is a thing to measure, not to change in passing.)
+constexpr int DUO_NPL = 0;
+// (role P also keeps its own x_n rows — fuel, engine: nobody else writes them — in registers, DuoEmit::xn_r, refreshed from the panel at every
+// stage 0: its emits — the last thing of its evaluation, behind role D's point X — then start without an LDS round trip. The Cessna172Sv0 instances:
+// the Xv2 ones spill with it.)
 // how many of role D's seventeen live in LDS; the rest — from the end: the angular / linear velocity rows, whose emit closes the evaluation
 // behind role P's point W, on the critical path of the pair — in registers (a ds_read + ds_write less per row and evaluation)
 // (the WA Cessna172Sv0 instance: 13 in LDS, four in registers, 248 registers: 14.36 -> 14.26 ms per launch, profiles/r04_ab_acc_regs.txt; the
 // ECEF / NED Cessna172Sv0 instances sit at 252-256 registers and would spill: all seventeen in LDS)
-#ifndef FB_DUO_NDL
-#define FB_DUO_NDL 13
-#endif
+constexpr int DUO_NDL_WA = 13;
 // (the Cessna172Xv2 instances, since the update halves are inlined: 14 in LDS, three in registers, no spill: 9.95 -> 9.86 ms per launch)
-#ifndef FB_DUO_NDL_X
-#define FB_DUO_NDL_X 14
-#endif
-template <int KIN, bool X> constexpr int duo_ndl() { return (KIN == FB_KIN_WA && !X) ? FB_DUO_NDL : (X ? FB_DUO_NDL_X : DUO_ND); }
-static_assert(FB_DUO_NDL >= 1 && FB_DUO_NDL <= DUO_ND, "");
+constexpr int DUO_NDL_X = 14;
+template <int KIN, bool X> constexpr int duo_ndl() { return (KIN == FB_KIN_WA && !X) ? DUO_NDL_WA : (X ? DUO_NDL_X : DUO_ND); }
+static_assert(DUO_NDL_WA >= 1 && DUO_NDL_WA <= DUO_ND && DUO_NDL_X >= 1 && DUO_NDL_X <= DUO_ND, "");
 // Per-aircraft launch constants cost a role twenty registers each if they ride through the evaluation. Role D reads the payload's
 // ten mass-property sums from an LDS panel at the point of use and fetches its aerodynamic sums from global memory at the start of
 // the evaluation (one batch of loads, consumed after the table locations).
@@ -1332,24 +1265,15 @@ struct DuoSync {
 // adds vmcnt(0) on this compiler: it would stall role D on its aerodynamic constants' global loads at every point, so the wait is
 // written out). The ACQUIRE side needs no instruction of its own: the poll's ds_read has returned (lgkmcnt(0) ahead of the
 // v_readfirstlane that consumes it) before any LDS access below the loop is issued, and the LDS performs one wave's accesses in issue
-// order. -DFB_DUO_RELEASE_WAIT=0 builds the round-3 form (compiler barriers only; it rests on that in-order service for the stores
-// too) for A/B timing: profiles/r04_ab_fence.txt.
-#ifndef FB_DUO_RELEASE_WAIT
-#define FB_DUO_RELEASE_WAIT 1
-#endif
+// order. (The round-3 form, compiler barriers only, rests on that in-order service for the stores too, which the hardware does not
+// promise; the wait costs +0.07-0.10 ms per launch: profiles/r04_ab_fence.txt.)
 // GLOBAL: the release also covers this wave's global-memory traffic (vmcnt(0): the Cessna172Xv2 instance hands values over through global
 // memory too — the evaluation's aerodynamic sums, the tapped outputs of a control update; the two waves of a pair share their CU's vector
 // L1, so a workgroup-scope release / acquire needs no cache maintenance).
 template <bool GLOBAL = false>
 FBD void duo_publish(DuoSync& sy, int k) {
     if constexpr (GLOBAL) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else {
-#if FB_DUO_RELEASE_WAIT
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (and, for the compiler: every LDS access above stays above ...)
-#else
-        asm volatile("" ::: "memory");   // (compiler: every LDS access above stays above ...)
-#endif
-    }
+    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (and, for the compiler: every LDS access above stays above ...)
     *sy.mine = sy.base + k + 1;
     asm volatile("" ::: "memory");   // (... and every one below stays below)
 }
@@ -1395,7 +1319,7 @@ struct DuoEmit {
     using SV = StateLds<DUO_B, false>;
     lds_cptr xs_l;     // x_n panel
     lds_ptr xwr_l;     // the panel this stage writes
-    lds_ptr acc_l;     // this role's stage sums in LDS: D's seventeen [17][DUO_B], the first DUO_NPL of P's four
+    lds_ptr acc_l;     // this role's stage sums in LDS: the first NDL of D's seventeen [NDL][DUO_B], the first DUO_NPL of P's four
     double* acc_r;     // the rest of the role's stage sums (registers)
     lds_ptr xch_l;     // exchange rows 6.. [XD_ROWS - 6][DUO_B]
     lds_ptr xov_l;     // exchange rows 0-5: the angular / linear velocity rows of the evaluation panel (see c172_duo_device.hpp)
@@ -1405,8 +1329,7 @@ struct DuoEmit {
     DuoSync* sync;     // this wave's side of the pair's synchronisation counters
     bool tap;          // wave-uniform (Cessna172Xv2): this is the step's last f_ode! and a control update follows it
     int64_t ai;        // the lane's aircraft
-    const double* xn_r = nullptr;   // role P (FB_DUO_P_XN_REGS): x_n of its own rows
-    GeoidCache* gcache = nullptr;   // role P (FB_DUO_GEOID_CACHE): the EGM96 cell of the lane's aircraft, kept from evaluation to evaluation
+    const double* xn_r = nullptr;   // role P, Cessna172Sv0: x_n of its own rows
     // rows k0 .. k0 + N - 1 of KArgs::duo_tap (base and stride re-read from the kernel's arguments: once per control period, see kernarg())
     template <int N>
     __device__ __forceinline__ void tap_rows(int k0, const double (&v)[N]) const {
@@ -1436,7 +1359,7 @@ struct DuoEmit {
     __device__ __forceinline__ void operator()(int j, double kj) const {
         static_assert(ROLE == 1 || ROLE == 2, "");
         const int r = SV::row(j), idx = r * DUO_B + t;
-        const double xs = (ROLE == 1 && FB_DUO_P_XN_REGS && !X) ? xn_r[slot(r)] : xs_l[idx];
+        const double xs = (ROLE == 1 && !X) ? xn_r[slot(r)] : xs_l[idx];
         const double A = __builtin_fma(eb, kj, aget(r));
         aset(r, A * em);
         xwr_l[idx] = __builtin_fma(ee, last ? A : kj, xs);
@@ -1445,7 +1368,7 @@ struct DuoEmit {
     __device__ __forceinline__ void batch(int j0, const double (&k)[NE]) const {
         double xs[NE], A[NE];
 #pragma unroll
-        for (int e = 0; e < NE; e++) { const int r = SV::row(j0 + e); xs[e] = (ROLE == 1 && FB_DUO_P_XN_REGS && !X) ? xn_r[slot(r)] : xs_l[r * DUO_B + t]; A[e] = aget(r); }
+        for (int e = 0; e < NE; e++) { const int r = SV::row(j0 + e); xs[e] = (ROLE == 1 && !X) ? xn_r[slot(r)] : xs_l[r * DUO_B + t]; A[e] = aget(r); }
 #pragma unroll
         for (int e = 0; e < NE; e++) A[e] = __builtin_fma(eb, k[e], A[e]);
 #pragma unroll
@@ -1495,7 +1418,6 @@ enum { DUO_C_EXIT = 4, DUO_C_TAP = 8, DUO_C_CMD = 16 };            // per-pair c
 //   * no derivative is carried across launches (k_step_air<X> saves one evaluation in 201 that way): a.k1_valid is cleared for the lanes
 //     whose steps are committed here; a lane handed over keeps the one the ground-capable pass left it (see the epilogue).
 constexpr int DUO_PT_U = DUO_NPT, DUO_PT_F = DUO_NPT;   // (behind the evaluation's points) role D: flags of the update written; role P: its half of the update done
-constexpr int DUO_PT_Z = DUO_NPT + 1;                   // role D (inside its half of an update): the pitch-axis outer loops' elevator reference put (x2_periodic_half)
 // Diagnostic builds (-DFB_STAMP -DFB_DUO_PHASES, tools/duo_phases.py): the shader clock when role D's first wave of workgroup 0 passes the
 // phases of a launch (g_stamp_acc[8 + k]: 0 entry, 1 tables staged, 2 state loaded and launch constants formed, 3 last evaluation done, 4 exit)
 #if defined(FB_STAMP) && defined(FB_DUO_PHASES)
@@ -1510,7 +1432,7 @@ constexpr int DUO_PT_Z = DUO_NPT + 1;                   // role D (inside its ha
 template <int KIN, bool X = false, bool PERENV = false>
 __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     constexpr int B = DUO_B, NR = FB_NX - 6, NP = DUO_NP, ND = DUO_ND;
-    constexpr int NPT = X ? DUO_NPT + 2 : DUO_NPT;   // points per iteration of the evaluation loop
+    constexpr int NPT = X ? DUO_NPT + 2 : DUO_NPT;   // points per iteration of the evaluation loop (Cessna172Xv2: U / F, and one number that is free since a fifth point was removed)
     constexpr int NAL = FB_ACT_BRAKE_LEFT;           // actuators the airborne evaluation reads
     using SV = StateLds<B, false>;
     __shared__ double lds[AT_SIZE + PT_SIZE];   // aero | piston tables (the propeller table stays in global memory, see rhs_duo())
@@ -1539,28 +1461,12 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     // P raced ahead on the shared fp64 pipe, then sat in the barrier while D ran alone with nobody to fill its stalls. With D ahead in
     // priority P fills D's gaps instead: 16.64 -> 15.95 ms per launch (profiles/r03_ab_prio.txt; s_setprio 1, 2, 3 and D in waves 0-3
     // measure alike).
-#ifndef FB_DUO_PRIO_D
-#define FB_DUO_PRIO_D 2
-#endif
-#ifndef FB_X2_LON_PRIO
-#define FB_X2_LON_PRIO 3   // Cessna172Xv2: role P's wave during its half of a control update (see there)
-#endif
-#ifndef FB_X2_HEAD_PRIO
-#define FB_X2_HEAD_PRIO 3  // ... and from the top of its loop to its point R
-#endif
-#ifndef FB_X2_UPD_PRIO
-#define FB_X2_UPD_PRIO 0   // ... and role D's wave during ITS half (the shorter one): 9.86 -> 9.82 ms per launch
-#endif
-#ifndef FB_X2_PITCH_PRIO
-#define FB_X2_PITCH_PRIO 3 // ... and role D's wave from the start of its half to its point Z (the pitch-axis outer loops, which role P's LQR waits for)
-#endif
-#ifndef FB_X2_SPEC_PRIO
-#define FB_X2_SPEC_PRIO 3  // ... and while it forms the next stage's aerodynamic sums at the end of an iteration
-#endif
-    if (role == 2) __builtin_amdgcn_s_setprio(FB_DUO_PRIO_D);
-#ifdef FB_DUO_PRIO_P
-    if (role == 1) __builtin_amdgcn_s_setprio(FB_DUO_PRIO_P);
-#endif
+    constexpr int DUO_PRIO_D = 2;
+    constexpr int X2_LON_PRIO = 3;    // Cessna172Xv2: role P's wave during its half of a control update (see there)
+    constexpr int X2_HEAD_PRIO = 3;   // ... and from the top of its loop to its point R
+    constexpr int X2_UPD_PRIO = 0;    // ... and role D's wave during ITS half (the shorter one): 9.86 -> 9.82 ms per launch
+    constexpr int X2_SPEC_PRIO = 3;   // ... and while it forms the next stage's aerodynamic sums at the end of an iteration
+    if (role == 2) __builtin_amdgcn_s_setprio(DUO_PRIO_D);
     const int t = threadIdx.x & (B - 1);
     const int pair = __builtin_amdgcn_readfirstlane(t >> 6);
     const int64_t i = (int64_t)blockIdx.x * B + t;
@@ -1605,23 +1511,12 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
         return k;
     };
     // one half of a control update (the arguments re-read from the kernel's argument block where the call stands: kernarg())
-    // The elevator reference of the pitch-axis outer loops, from the lateral half's wave (role D's) to the longitudinal half's (role P's): through
-    // the lane's slot of the exchange row that carries h_rot during an evaluation (role P writes it ahead of its point W, role D reads it behind W:
-    // idle between evaluations, like the rho / h_o rows that carry the lateral commands) and role D's point Z (an LDS-only release: what crosses is
-    // this one row). NOT the evaluation panel's velocity rows: the tapped evaluation is stage 0 of the next step, its emits have left the stage-1
-    // state there.
-    struct CtlHand {
-        lds_ptr slot; DuoSync* sy;
-        __device__ __forceinline__ void put(double v) const { *slot = v; duo_publish<false>(*sy, DUO_PT_Z); __builtin_amdgcn_s_setprio(FB_X2_UPD_PRIO); }
-        __device__ __forceinline__ double get() const { duo_wait(*sy, DUO_PT_Z); return *slot; }
-    };
     [[maybe_unused]] auto ctl_half = [&](auto half, int64_t lane) {
         const kargs_cptr ka = kernarg();
         auto pk = [&](int k) { return (uint32_t)ka->ctl_off.off[k] | ((uint32_t)ka->ctl_off.off[k + 1] << 16); };
-        const CtlHand hand = {(lds_ptr)xch_l + (XD_HROT - 6) * B + t, &sy};
         return x2_periodic_half<decltype(half)::value>(ka->cu, ka->cs, ka->gains, ka->duo_tap, ka->n, ka->ctl_dT, pk(0), pk(2), pk(4), pk(6), pk(8),
                                                        (uint32_t)ka->ctl_off.total | ((uint32_t)ka->ctl_off.same_grid << 16), lane,
-                                                       xs_l[SV::row(h_e_row<KIN>()) * B + t], (lds_cptr)xs_l + t, hand);
+                                                       xs_l[SV::row(h_e_row<KIN>()) * B + t], (lds_cptr)xs_l + t);
     };
     if (role == 1) {
         // ================= role P =================
@@ -1636,9 +1531,8 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 for (int k = 0; k < NAL; k++) { xa[k] = a.x[(int64_t)(X2_ACT + k) * a.n + i]; ca[k] = x2_command(a, i, k); }
                 in.mixture = clampd(a.u[(int64_t)FB_U_MIXTURE * a.n + i], 0, 1);
                 in.ui = a.ui[i];
-                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP) {   // its half of the launch-start copy of the control-law record (role D copies cu); not for a launch of one step: see k_step_air
-                    static_assert(FB_NCS % 11 == 0 && FB_NCU % 14 == 0 && FB_NCS % FB_X2_BAK_G_CS == 0 && FB_NCU % FB_X2_BAK_G_CU == 0, "batch sizes of the record copies");
-                    copy_rows_batched<FB_NCS, FB_X2_BAK_G_CS>(a.ctl_bak, a.cs, a.n, i);
+                if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP) {   // its half of the launch-start copy of the control-law record (role D copies cu); not for a launch of one step: see k_step_air
+                    copy_rows_batched<FB_NCS, CTL_BAK_G_CS>(a.ctl_bak, a.cs, a.n, i);
                 }
             }
             // once per launch: the backup rows have left this wave before its first publication, whichever kind that is — role D restores a
@@ -1651,7 +1545,6 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
         }
         double acc_r[NP - DUO_NPL];
         double xn_r[NP] = {0, 0, 0, 0};
-        GeoidCache gcache = {-1, -1, 0.0f, 0.0f, 0.0f, 0.0f};   // (no cell yet: the first evaluation gathers)
 #pragma unroll
         for (int k = 0; k < NP - DUO_NPL; k++) acc_r[k] = 0.0;
 #pragma unroll
@@ -1670,7 +1563,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
             const double ms = act_stage_mc(stg_for, z);
             double xa_s[FB_NACT];
 #pragma unroll
-            for (int k = 0; k < NAL; k++) xa_s[k] = act_stage_pos(xa[k], ca[k], ms, stg_for == 0);
+            for (int k = 0; k < NAL; k++) xa_s[k] = act_stage_pos(xa[k], ca[k], ms);
             xa_s[FB_ACT_BRAKE_LEFT] = 0; xa_s[FB_ACT_BRAKE_RIGHT] = 0;   // (never read in the air)
             const InputsX ix = {xa_s, nullptr, a.n, in.ui};
             // InputsAgg::sum_aero's expressions, term by term; the flap-dependent ones (two table locations, three lookups, five of the ten
@@ -1704,7 +1597,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
             DUO_MARK(1, 15);  // (arrival at the top of the loop, counted from the previous evaluation's start)
             duo_wait(sy, DUO_PT_T);   // role D's control and flag words of this evaluation are written, every row of the previous one emitted
             DUO_MARK(1, 0);
-            if constexpr (X) __builtin_amdgcn_s_setprio(FB_X2_HEAD_PRIO);   // (until its point R: role D reads the evaluation's sums behind it, early in its own evaluation)
+            if constexpr (X) __builtin_amdgcn_s_setprio(X2_HEAD_PRIO);   // (until its point R: role D reads the evaluation's sums behind it, early in its own evaluation)
             const int c = __builtin_amdgcn_readfirstlane(ctrl_l[pair]);
             const int f = flags_l[t];
             if constexpr (X) {
@@ -1722,7 +1615,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 for (int k = 0; k < DUO_NPL; k++) accp_l[k * B + t] = 0.0;
             }
             const int stg = c & 3;
-            if (FB_DUO_P_XN_REGS && !X && stg == 0) {
+            if (!X && stg == 0) {
 #pragma unroll
                 for (int k = 0; k < NP; k++) xn_r[k] = xs_l[(2 + k) * B + t];
             }
@@ -1743,12 +1636,12 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                         double z = z0;
                         asm volatile("" : "+v"(z));   // (opaque: the stage multipliers are formed here, not hoisted out of the loop into registers that then spill)
                         const double ms = act_stage_mc(stg, z);
-                        inl.throttle = clampd(act_stage_pos(xa[FB_ACT_THROTTLE], ca[FB_ACT_THROTTLE], ms, stg == 0), 0.0, 1.0);   // InputsX::get_throttle
+                        inl.throttle = clampd(act_stage_pos(xa[FB_ACT_THROTTLE], ca[FB_ACT_THROTTLE], ms), 0.0, 1.0);   // InputsX::get_throttle
                     }
                     DUO_MARK(1, 12);   // (Cessna172Xv2: stage positions and aerodynamic sums formed and stored)
                     asm volatile("" : "+v"(inl.throttle), "+v"(inl.mixture));
                     const DuoEmit<1, X> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accp_l, acc_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
-                                                tap, i, xn_r, &gcache};
+                                                tap, i, xn_r};
                     if constexpr (X) {
                         if (tap) {   // what the control laws read of the actuators: the Ranged positions of the state x_{n+1} (InputsX::pos), and the commands this f_ode! saw
                             static_assert(DUO_TAP_CMD == DUO_TAP_POS + 4, "positions, then commands");
@@ -1793,7 +1686,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     // (issue priority: this half is the longer one and runs ahead of role D's; role D waits for it at priority 0. Measured —
                     // profiles/r04_x2_update_ab.txt — the two halves do not overlap at role D's stepping priority: 0.156 ms per update of
                     // 524 288 aircraft against 0.078 + 0.061 for the halves alone; with this half ahead 0.115)
-                    __builtin_amdgcn_s_setprio(FB_X2_LON_PRIO);
+                    __builtin_amdgcn_s_setprio(X2_LON_PRIO);
 #ifdef FB_X2_SKIP_LON   // (timing diagnostics: one half of the update alone)
                     if (false) {
 #else
@@ -1808,16 +1701,14 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 }
                 // the sums of the stage that normally comes next, while role D finishes its evaluation and keeps the book — unless a control
                 // update has just run: role D's two new commands arrive with the next control word, and the sums are formed then, once
-#ifndef FB_X2_NO_SPECULATION
                 if (tap) sums_for = -1;
                 else {
                     // (ahead of role D in issue priority: this wave must be back at the top, and through its state reads, before role D needs
                     // point R — at priority 0 it got there late: stepping alone 8.52 -> 8.33 ms, profiles/r04_x2_update_ab.txt)
-                    __builtin_amdgcn_s_setprio(FB_X2_SPEC_PRIO);
+                    __builtin_amdgcn_s_setprio(X2_SPEC_PRIO);
                     form_sums((stg + 1) & 3, lds_off);
                     __builtin_amdgcn_s_setprio(0);
                 }
-#endif
             }
             sy.base += NPT;
         }
@@ -1867,8 +1758,8 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     for (int k = 0; k < 10; k++) a.duo_pld[(int64_t)k * a.n + i] = pv[k];
                 }
                 in.ui = in0.ui;
-                if (FB_X2_BAK && a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP && !to_ground) {   // its half of the launch-start copy of the control-law record (role P copies cs)
-                    copy_rows_batched<FB_NCU, FB_X2_BAK_G_CU>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, i);
+                if (a.ctl_ratio > 0 && nsteps > FB_CTL_BAK_SKIP && !to_ground) {   // its half of the launch-start copy of the control-law record (role P copies cs)
+                    copy_rows_batched<FB_NCU, CTL_BAK_G_CU>(a.ctl_bak + (int64_t)FB_NCS * a.n, a.cu, a.n, i);
                 }
             } else {
                 InputsAgg in0;
@@ -1900,11 +1791,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     if ((threadIdx.x & 63) == 0) ctrl_l[pair] = exit_ ? DUO_C_EXIT : 0;
     // (this lane's launch constants — Sv0: aerodynamic, Xv2: payload — are read back from memory by THIS lane: program order is all that needs,
     // no fence. The device-scope __threadfence() that stood here wrote the L2 back — buffer_wbl2 — in every wave of every workgroup.)
-#ifdef FB_DUO_START_FENCE
-    __threadfence();
-#elif !defined(FB_DUO_START_NOWAIT)
     __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the stores have been performed at this XCD's L2, which every later load of this workgroup goes to
-#endif
 #pragma unroll 1
     while (true) {
         DUO_MARK(2, 15);
@@ -2027,7 +1914,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 // does not touch). Role P's wave runs the longitudinal half meanwhile.
                 DUO_MARK(2, 12);   // f_step! done, flags written: at U
                 duo_publish<true>(sy, DUO_PT_U);
-                __builtin_amdgcn_s_setprio(FB_X2_SPLIT_PITCH ? FB_X2_PITCH_PRIO : FB_X2_UPD_PRIO);   // (its half is the shorter one: behind role P's, which runs at FB_X2_LON_PRIO; FB_X2_SPLIT_PITCH: ahead up to its point Z, CtlHand::put)
+                __builtin_amdgcn_s_setprio(X2_UPD_PRIO);   // (its half is the shorter one: behind role P's, which runs at X2_LON_PRIO)
 #ifdef FB_X2_SERIAL   // (timing diagnostic: the lateral half only after the longitudinal one has finished)
                 duo_wait(sy, DUO_PT_F);
 #endif
@@ -2043,10 +1930,8 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 DUO_MARK(2, 13);   // lateral half done
                 __builtin_amdgcn_s_setprio(0);
                 duo_wait(sy, DUO_PT_F);   // role P's half is done: the record is at rest
-                __builtin_amdgcn_s_setprio(FB_DUO_PRIO_D);
-#ifdef FB_X2_UPD_PRIO
-                __builtin_amdgcn_s_setprio(FB_DUO_PRIO_D);
-#endif
+                __builtin_amdgcn_s_setprio(DUO_PRIO_D);
+                __builtin_amdgcn_s_setprio(DUO_PRIO_D);   // (a second time, as in every build so far: dropping it changes the shipped code, which is a change for a measurement to carry)
                 DUO_MARK(2, 14);   // past F
             }
             // the evaluation to come is the last f_ode! of a step that closes a control period?
@@ -2192,12 +2077,9 @@ __device__ __forceinline__ void trim_assign(const TrimP& p, const double* z, con
     in.n = 0;
 }
 // residuals whose squared sum is the reference's cost (c172.jl:857-867)
-// (FB_TRIM_FAST_RHS: the evaluation in the stepping kernels' form — their atan2 / log / sincos, knot scans through scalar loads — instead of
+// (the evaluation in the stepping kernels' form — their atan2 / log / sincos, knot scans through scalar loads — instead of
 // the single-call verbs' form with the library's: a third of the instructions, and the trimmed state is the zero of the very arithmetic
 // that steps it. The trim state moves by ~1e-13 against the library form.)
-#ifndef FB_TRIM_FAST_RHS
-#define FB_TRIM_FAST_RHS true
-#endif
 // GROUND = false: the airborne-only evaluation (388 registers against 504); answers FB_ST_INTERNAL_REDO where a wheel could reach the ground
 template <bool GROUND = true>
 __device__ __forceinline__ int32_t trim_resid_body(const TrimP& p, const double* z, const Env& env, const Tables& T, double* r) {
@@ -2207,7 +2089,7 @@ __device__ __forceinline__ int32_t trim_resid_body(const TrimP& p, const double*
     double uraw[FB_NU];
     trim_assign(p, z, env, T, x, in, uraw);
     StepAux aux;
-    const int32_t st = rhs<FB_KIN_WA, GROUND, FB_TRIM_FAST_RHS>(x, 0, 2, in, env, T, [&](int j, double v) { xd[j] = v; }, aux, NoSink{});
+    const int32_t st = rhs<FB_KIN_WA, GROUND, true>(x, 0, 2, in, env, T, [&](int j, double v) { xd[j] = v; }, aux, NoSink{});
     const double nv = sqrt(x[FB_X_V_EB_B] * x[FB_X_V_EB_B] + x[FB_X_V_EB_B + 1] * x[FB_X_V_EB_B + 1] + x[FB_X_V_EB_B + 2] * x[FB_X_V_EB_B + 2]);
     r[0] = xd[FB_X_V_EB_B] / nv; r[1] = xd[FB_X_V_EB_B + 1] / nv; r[2] = xd[FB_X_V_EB_B + 2] / nv;
     r[3] = xd[FB_X_OMEGA_EB_B]; r[4] = xd[FB_X_OMEGA_EB_B + 1]; r[5] = xd[FB_X_OMEGA_EB_B + 2];
@@ -2360,13 +2242,11 @@ __device__ __forceinline__ void trim_leave_body(const KArgs& a, const Env& env, 
 constexpr double TRIM_LO[TRIM_N] = {-PI / 12, -PI / 3, 0.4, 0, -1, -1, -1};                 // c172.jl:901-908
 constexpr double TRIM_HI[TRIM_N] = {c172::alpha_stall_hi, PI / 3, 1.1, 1, 1, 1, 1};         // c172.jl:910-917
 constexpr int TRIM_MAX_ITER = 500;
-#ifndef FB_TRIM_REFILL_MIN
-#define FB_TRIM_REFILL_MIN 16   // (4: 77.6 ms, 8: 73.8, 16: 72.0, 24: 74.5 per 1 048 576 aircraft of the bench lattice)
-#endif
+constexpr int TRIM_REFILL_MIN = 16;   // (4: 77.6 ms, 8: 73.8, 16: 72.0, 24: 74.5 per 1 048 576 aircraft of the bench lattice)
 // The descent from the given trim state, for every aircraft.
 //  * PERSISTENT: the aircraft differ in how many iterations they take (bench lattice: 64 to 606 residual evaluations, mean 144 — a wave that
 //    trimmed 64 aircraft side by side waited for its slowest, ~420). One wave per SIMD; a wave takes aircraft from a queue (`next`, zeroed by the
-//    host), every lane descends on its own aircraft, and when FB_TRIM_REFILL_MIN lanes have finished theirs they are served together: results
+//    host), every lane descends on its own aircraft, and when TRIM_REFILL_MIN lanes have finished theirs they are served together: results
 //    written, the next aircraft taken.
 //  * ONE loop around ONE inlined residual evaluation, no call: with the residual out of line (an `f_ode!`: ~7.6 k instructions, every VGPR) each
 //    call saved and restored the callee-saved registers and the caller's arrays through scratch — 800 scratch accesses per evaluation, a scratch
@@ -2430,7 +2310,7 @@ __global__ __launch_bounds__(64) void k_trim(KArgs a, const double* tp, double* 
     for (;;) {
         const unsigned long long idle = __builtin_amdgcn_ballot_w64(!active);
         const int n_idle = __builtin_popcountll(idle);
-        if (n_idle == 64 || (more && n_idle >= FB_TRIM_REFILL_MIN)) {
+        if (n_idle == 64 || (more && n_idle >= TRIM_REFILL_MIN)) {
             TRIM_MARK(0);
             if (!active && i >= 0) {   // assign!(vehicle, params, state_opt) with the REQUESTED parameters
                 TrimP p;

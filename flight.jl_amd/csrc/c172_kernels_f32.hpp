@@ -38,11 +38,8 @@ FBD constexpr int xsrow(int r) { return r < RP0 ? r : r - XPN; }   // panel row 
 // emit of the fp32 stepper. The stage enters through wave-uniform scalar branches (not through selects as in the fp64 kernel: with
 // two waves per SIMD the SALU work of one wave hides behind the other's VALU, and VALU issue is what bounds this kernel), one
 // branch per BATCH of consecutive rows: all panel reads first, then the updates and writes, so the LDS round trips of a batch overlap.
-// FB_F32_NAL: how many of the 21 stage sums (k1 + 2 k2 + 2 k3) live in LDS; the rest, from the last panel row down, in registers
-#ifndef FB_F32_NAL
-#define FB_F32_NAL 9   // (12 in registers: 7.92 -> 7.66 ms per launch, profiles/r04_ab_acc_regs.txt; 249 registers, the LDS panel 37 KB smaller per CU)
-#endif
-constexpr int F32_NAL = FB_F32_NAL;
+// F32_NAL: how many of the 21 stage sums (k1 + 2 k2 + 2 k3) live in LDS; the rest, from the last panel row down, in registers
+constexpr int F32_NAL = 9;   // (12 in registers: 7.92 -> 7.66 ms per launch, profiles/r04_ab_acc_regs.txt; 249 registers, the LDS panel 37 KB smaller per CU)
 template <int B>
 struct F32Emit {
     typedef void batched_tag;

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "c172_kernels.hpp"
 #include "c172x_kernels.hpp"
@@ -101,7 +102,6 @@ static KArgs make_args(fb_handle h) {
     a.env_rows = h->env_rows;
     a.dt = h->params.dt;
     a.cs = h->cs; a.cu = h->cu; a.q_pre = h->q_pre; a.redo = h->redo; a.k1 = h->k1; a.k1_valid = h->k1_valid;
-    if (getenv("FB_NO_FSAL_CARRY")) a.k1 = nullptr;   // A/B switch for measurements
     a.gains = h->gains; a.ctl_bak = h->ctl_bak; a.duo_pld = h->duo_pld; a.duo_tap = h->duo_tap;
     a.term_step = h->term_step; a.term_where = h->term_where; a.step0 = h->steps_done;
     for (int k = 0; k < 10; k++) a.ctl_off.off[k] = (int)h->gains_off[k];
@@ -168,65 +168,22 @@ static row_map_t row_map_of(fb_handle h) {
     if (h->kin == FB_KIN_NED) return ned_dev_row;
     return nullptr;
 }
-// one launch statement per (model, kinematics) instance of a kernel template
-#define FB_LAUNCH_MK(KERNEL, GRID, BLOCK, ...)                                                                                       \
-    do {                                                                                                                              \
-        if (is_x2(h) && h->kin == FB_KIN_ECEF) hipLaunchKernelGGL((KERNEL<true, FB_KIN_ECEF>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); \
-        else if (is_x2(h) && h->kin == FB_KIN_NED) hipLaunchKernelGGL((KERNEL<true, FB_KIN_NED>), GRID, BLOCK, 0, h->stream, __VA_ARGS__); \
-        else if (is_x2(h)) hipLaunchKernelGGL((KERNEL<true, FB_KIN_WA>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);                     \
-        else if (h->kin == FB_KIN_ECEF) hipLaunchKernelGGL((KERNEL<false, FB_KIN_ECEF>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);     \
-        else if (h->kin == FB_KIN_NED) hipLaunchKernelGGL((KERNEL<false, FB_KIN_NED>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);       \
-        else hipLaunchKernelGGL((KERNEL<false, FB_KIN_WA>), GRID, BLOCK, 0, h->stream, __VA_ARGS__);                                  \
-    } while (0)
+// The handle's run-time (model, mechanisation) as compile-time values: f(KIN) / f(X, KIN) with std::integral_constant arguments, so that a
+// generic lambda names the kernel instance — one launch statement per kernel template, every (model, kinematics) instance of it instantiated
+template <class F>
+static void with_kin(fb_handle h, F&& f) {
+    if (h->kin == FB_KIN_ECEF) f(std::integral_constant<int, FB_KIN_ECEF>{});
+    else if (h->kin == FB_KIN_NED) f(std::integral_constant<int, FB_KIN_NED>{});
+    else f(std::integral_constant<int, FB_KIN_WA>{});
+}
+template <class F>
+static void with_model_kin(fb_handle h, F&& f) {
+    if (is_x2(h)) with_kin(h, [&](auto KIN) { f(std::true_type{}, KIN); });
+    else with_kin(h, [&](auto KIN) { f(std::false_type{}, KIN); });
+}
 // FLIGHTBATCH_DUO (read when a handle is created; A/B switch for measurements): Cessna172Sv0 and Cessna172Xv2 in fp64 (any mechanisation) are stepped
 // by the wave-specialised k_step_duo<KIN, X> (two waves per SIMD) unless it is 0, which selects the one-wave-per-SIMD k_step_air<KIN, X>
 static bool env_step_duo() { const char* e = getenv("FLIGHTBATCH_DUO"); return e ? atoi(e) != 0 : true; }
-// the two passes of the stepping kernel (airborne instance, then the ground-capable one over the lanes it handed over)
-#define FB_STEP_PERENV(KIN, X, GRID, A, K)                                                                                            \
-    do {   /* per-aircraft environment rows (KArgs::env_rows): the wave-pair kernel in every mechanisation (FB_F32 handles: the one-wave fp64 kernel) */ \
-        if (h->duo) hipLaunchKernelGGL((k_step_duo<KIN, X, true>), grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, A, K);         \
-        else hipLaunchKernelGGL((k_step_air<KIN, X, false, true>), GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                      \
-        hipLaunchKernelGGL((k_step_air<KIN, X, true, true>), grid_for(h->n, step_block<X, true>()), dim3(step_block<X, true>()), 0, h->stream, A, K); \
-    } while (0)
-#define FB_STEP_X2(KIN, GRID, A, K)                                                                                                   \
-    do {                                                                                                                              \
-        if (h->env_rows) { FB_STEP_PERENV(KIN, true, GRID, A, K); break; }                                                            \
-        if (h->duo) hipLaunchKernelGGL((k_step_duo<KIN, true>), grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, A, K);         \
-        else hipLaunchKernelGGL((k_step_air<KIN, true>), GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                                \
-        hipLaunchKernelGGL((k_step_air<KIN, true, true>), grid_for(h->n, step_block<true, true>()), dim3(step_block<true, true>()), 0, h->stream, A, K); \
-    } while (0)
-// the Cessna172Xv2 kernels that are not stepping kernels take the mechanisation alone
-#define FB_LAUNCH_X2K(KERNEL, N, ...)                                                                                                 \
-    do {                                                                                                                              \
-        if (h->kin == FB_KIN_ECEF) hipLaunchKernelGGL(KERNEL<FB_KIN_ECEF>, grid_for(N, 256), dim3(256), 0, h->stream, __VA_ARGS__);  \
-        else if (h->kin == FB_KIN_NED) hipLaunchKernelGGL(KERNEL<FB_KIN_NED>, grid_for(N, 256), dim3(256), 0, h->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<FB_KIN_WA>, grid_for(N, 256), dim3(256), 0, h->stream, __VA_ARGS__);                          \
-    } while (0)
-#define FB_LAUNCH_STEP(GRID, A, K)                                                                                                    \
-    do {                                                                                                                              \
-        if (is_x2(h) && h->kin == FB_KIN_ECEF) FB_STEP_X2(FB_KIN_ECEF, GRID, A, K);                                                   \
-        else if (is_x2(h) && h->kin == FB_KIN_NED) FB_STEP_X2(FB_KIN_NED, GRID, A, K);                                                \
-        else if (is_x2(h)) FB_STEP_X2(FB_KIN_WA, GRID, A, K);                                                                         \
-        else if (h->env_rows && h->kin == FB_KIN_ECEF) FB_STEP_PERENV(FB_KIN_ECEF, false, GRID, A, K);                                \
-        else if (h->env_rows && h->kin == FB_KIN_NED) FB_STEP_PERENV(FB_KIN_NED, false, GRID, A, K);                                  \
-        else if (h->env_rows) FB_STEP_PERENV(FB_KIN_WA, false, GRID, A, K);   /* (FB_F32 handles too: the fp32 stepper is batch-wide only) */ \
-        else if (h->kin == FB_KIN_ECEF) {                                                                                           \
-            if (h->duo) hipLaunchKernelGGL(k_step_duo<FB_KIN_ECEF>, grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, A, K);  \
-            else hipLaunchKernelGGL(k_step_air<FB_KIN_ECEF>, GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                            \
-            hipLaunchKernelGGL((k_step_air<FB_KIN_ECEF, false, true>), grid_for(h->n, step_block<false, true>()), dim3(step_block<false, true>()), 0, h->stream, A, K);                  \
-        } else if (h->kin == FB_KIN_NED) {                                                                                            \
-            if (h->duo) hipLaunchKernelGGL(k_step_duo<FB_KIN_NED>, grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, A, K);   \
-            else hipLaunchKernelGGL(k_step_air<FB_KIN_NED>, GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                             \
-            hipLaunchKernelGGL((k_step_air<FB_KIN_NED, false, true>), grid_for(h->n, step_block<false, true>()), dim3(step_block<false, true>()), 0, h->stream, A, K);                   \
-        } else if (h->dtype == FB_F32) {   /* fp32 airborne stepper; lanes near the ground go to the fp64 ground-capable kernel */    \
-            hipLaunchKernelGGL(fbf::k_step_f32, GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                                         \
-            hipLaunchKernelGGL((k_step_air<FB_KIN_WA, false, true>), grid_for(h->n, step_block<false, true>()), dim3(step_block<false, true>()), 0, h->stream, A, K);                    \
-        } else {                                                                                                                      \
-            if (h->duo) hipLaunchKernelGGL(k_step_duo<FB_KIN_WA>, grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, A, K);    \
-            else hipLaunchKernelGGL(k_step_air<FB_KIN_WA>, GRID, dim3(STEP_BLOCK), 0, h->stream, A, K);                              \
-            hipLaunchKernelGGL((k_step_air<FB_KIN_WA, false, true>), grid_for(h->n, step_block<false, true>()), dim3(step_block<false, true>()), 0, h->stream, A, K);                    \
-        }                                                                                                                             \
-    } while (0)
 static CtlArgs ctl_args(fb_handle h, int use_q_pre) {
     CtlArgs c;
     c.gains = h->gains;
@@ -394,7 +351,7 @@ static int32_t scn_evaluate(fb_handle h) {
     sc.prog = h->scn_prog; sc.n_ph = h->scn_nph; sc.n_rule = h->scn_nrule; sc.n_act = h->scn_nact; sc.n_par = h->scn_npar; sc.n_rec = h->scn_nrec;
     sc.phase = h->scn_phase; sc.since = h->scn_since; sc.par = h->scn_par; sc.rec = h->scn_rec;
     sc.step = h->steps_done; sc.dt = h->params.dt; sc.t = (double)h->steps_done * h->params.dt;   // sim.t = t_start + nstep dt with t_start = 0 (FC/sim.jl:261-275)
-    FB_LAUNCH_X2K(k_scenario, h->n, make_args(h), sc);
+    with_kin(h, [&](auto KIN) { hipLaunchKernelGGL(k_scenario<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -425,7 +382,7 @@ static int32_t trim_run(fb_handle h, const KArgs& a, const double* trim_params, 
     if (h->kin == FB_KIN_ECEF) hipLaunchKernelGGL(k_kin_convert<FB_KIN_ECEF>, grid_for(n, 256), dim3(256), 0, h->stream, a, (const double*)d_tp);
     if (h->kin == FB_KIN_NED) hipLaunchKernelGGL(k_kin_convert<FB_KIN_NED>, grid_for(n, 256), dim3(256), 0, h->stream, a, (const double*)d_tp);
     if (is_x2(h)) {  // f_init!(aircraft, trim): actuator states, then f_init!(avionics, vehicle) (aircraftbase.jl:255-265)
-        FB_LAUNCH_X2K(k_x2_init, n, a, ctl_args(h, 0));
+        with_kin(h, [&](auto KIN) { hipLaunchKernelGGL(k_x2_init<KIN.value>, grid_for(n, 256), dim3(256), 0, h->stream, a, ctl_args(h, 0)); });
         HIPCHK(hipGetLastError());
     }
     h->steps_done = 0;
@@ -733,7 +690,7 @@ int32_t fb_f_init(fb_handle h, const double* init, int32_t ninit) {
     if (is_x2(h) && ninit == 0) {   // f_init!(avionics, vehicle) on the state the host has set
         if (int32_t rc = check_ready_x2(h)) return rc;
         fsal_invalidate(h);
-        FB_LAUNCH_X2K(k_x2_init, h->n, make_args(h), ctl_args(h, 0));
+        with_kin(h, [&](auto KIN) { hipLaunchKernelGGL(k_x2_init<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), ctl_args(h, 0)); });
         HIPCHK(hipGetLastError());
         h->steps_done = 0;
         h->t = 0.0;
@@ -757,7 +714,9 @@ int32_t fb_f_ode(fb_handle h, double* xdot) {
     const int64_t n = h->n;
     if (!h->y) HIPCHK(hipMalloc(&h->y, sizeof(double) * FB_NY * n));
     if (xdot && !h->xdot) HIPCHK(hipMalloc(&h->xdot, sizeof(double) * (is_x2(h) ? (int)FB_X2_NX : (int)FB_NX) * n));
-    FB_LAUNCH_MK(k_f_ode, grid_for(n, 256), dim3(256), make_args(h), xdot ? h->xdot : (double*)nullptr, h->y);
+    with_model_kin(h, [&](auto X, auto KIN) {
+        hipLaunchKernelGGL((k_f_ode<X.value, KIN.value>), grid_for(n, 256), dim3(256), 0, h->stream, make_args(h), xdot ? h->xdot : (double*)nullptr, h->y);
+    });
     HIPCHK(hipGetLastError());
     if (xdot) {
         if (int32_t rc = copy_rows(h, h->xdot, nullptr, xdot, nx_of(h), row_map_of(h))) return rc;
@@ -776,7 +735,7 @@ int32_t fb_f_step(fb_handle h) {
     }
     if (int32_t rc = check_ready(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    FB_LAUNCH_MK(k_f_step, grid_for(h->n, 256), dim3(256), make_args(h));
+    with_model_kin(h, [&](auto X, auto KIN) { hipLaunchKernelGGL((k_f_step<X.value, KIN.value>), grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h)); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -792,7 +751,7 @@ int32_t fb_f_periodic(fb_handle h) {
     if (is_x2(h)) {  // f_periodic!(Unconditional(), world): the control laws on the outputs of an f_ode! at the current x
         if (int32_t rc = check_ready_x2(h)) return rc;
         HIPCHK(hipSetDevice(h->device));
-        FB_LAUNCH_X2K(k_x2_ctl, h->n, make_args(h), ctl_args(h, 0));
+        with_kin(h, [&](auto KIN) { hipLaunchKernelGGL(k_x2_ctl<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), ctl_args(h, 0)); });
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -864,6 +823,32 @@ int32_t fb_set_steps_per_launch(fb_handle h, int32_t k) {
     h->steps_per_launch = k;
     return 0;
 }
+// One launch of the stepping kernel = two passes: the airborne instance, then the ground-capable one over the lanes it handed over. PERENV:
+// per-aircraft environment rows (KArgs::env_rows) — the wave-pair kernel in every mechanisation; FB_F32 handles: the one-wave fp64 kernel (the fp32
+// stepper is batch-wide only, and Cessna172Sv0 / WA only: fb_create).
+// Every instance of k_step_duo (12) and k_step_air (24) is instantiated HERE, in the order in which the lambdas below first name them, and that
+// is the order of the kernels in the code object: the nesting (Cessna172Xv2: mechanisation, then environment; Cessna172Sv0: the other way round)
+// and the fp32 case ahead of the rest keep the order the library has always had, so that a change of this function shows as no change of the device code.
+static void launch_step(fb_handle h, dim3 grid, const KArgs& a, int k) {
+    auto ground_pass = [&](auto X, auto KIN, auto PERENV) {
+        constexpr int B = step_block<X.value, true>();
+        hipLaunchKernelGGL((k_step_air<KIN.value, X.value, true, PERENV.value>), grid_for(h->n, B), dim3(B), 0, h->stream, a, k);
+    };
+    auto passes = [&](auto X, auto KIN, auto PERENV) {
+        if constexpr (!X.value && KIN.value == FB_KIN_WA && !PERENV.value) {   // the one instance of the fp32 airborne stepper; its lanes near the ground go to the fp64 ground-capable kernel
+            if (h->dtype == FB_F32) {
+                hipLaunchKernelGGL(fbf::k_step_f32, grid, dim3(STEP_BLOCK), 0, h->stream, a, k);
+                return ground_pass(X, KIN, PERENV);
+            }
+        }
+        if (h->duo) hipLaunchKernelGGL((k_step_duo<KIN.value, X.value, PERENV.value>), grid_for(h->n, DUO_B), dim3(2 * DUO_B), 0, h->stream, a, k);
+        else hipLaunchKernelGGL((k_step_air<KIN.value, X.value, false, PERENV.value>), grid, dim3(STEP_BLOCK), 0, h->stream, a, k);
+        ground_pass(X, KIN, PERENV);
+    };
+    auto with_env = [&](auto&& f) { if (h->env_rows) f(std::true_type{}); else f(std::false_type{}); };
+    if (is_x2(h)) with_kin(h, [&](auto KIN) { with_env([&](auto PERENV) { passes(std::true_type{}, KIN, PERENV); }); });
+    else with_env([&](auto PERENV) { with_kin(h, [&](auto KIN) { passes(std::false_type{}, KIN, PERENV); }); });
+}
 // nsteps of the stepping kernel, no logging
 static int32_t step_raw(fb_handle h, int64_t nsteps) {
     if (h->model == FB_MODEL_ROBOT2D) return r2_step(h, nsteps);
@@ -886,7 +871,7 @@ static int32_t step_raw(fb_handle h, int64_t nsteps) {
         a.step0 = h->steps_done;
         const bool stamp = h->timing && h->lev_used < h->lev_max;
         if (stamp) HIPCHK(hipEventRecord(h->lev[2 * h->lev_used], h->stream));
-        FB_LAUNCH_STEP(grid_for(h->n, 256), a, k);
+        launch_step(h, grid_for(h->n, 256), a, k);
         if (stamp) { HIPCHK(hipEventRecord(h->lev[2 * h->lev_used + 1], h->stream)); h->lev_used++; }
         left -= k;
         h->steps_done += k;

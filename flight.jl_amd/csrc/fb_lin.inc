@@ -61,17 +61,16 @@ static int32_t lin_run(fb_handle h, const KArgs& a, int32_t scheme, const LinHos
     } else {
         const LinOut o = {xdot0, out.x0 ? x0 : nullptr, out.u0 ? u0 : nullptr, y0, want_ab ? AB : nullptr, want_cd ? CD : nullptr,
                           two ? tAB : nullptr, two ? tCD : nullptr, h->lin_st, scheme};
-#define FB_LIN_LAUNCH(X)                                                                                                              \
-        do {                                                                                                                          \
-            hipLaunchKernelGGL(k_lin_base<X>, gb, dim3(256), 0, h->stream, a, o);                                                     \
-            if (!want_ab && !want_cd) break;                                                                                          \
-            if (scheme == FB_LIN_FORWARD) { hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_FORWARD, 0>), gd, dim3(256), 0, h->stream, a, o); break; } \
-            hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_ONESIDED2, 0>), gd, dim3(256), 0, h->stream, a, o);                              \
-            hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_ONESIDED2, 1>), gd, dim3(256), 0, h->stream, a, o);                              \
-        } while (0)
-        if (is_x2(h)) FB_LIN_LAUNCH(true);
-        else FB_LIN_LAUNCH(false);
-#undef FB_LIN_LAUNCH
+        auto launch = [&](auto X_) {
+            constexpr bool X = decltype(X_)::value;
+            hipLaunchKernelGGL(k_lin_base<X>, gb, dim3(256), 0, h->stream, a, o);
+            if (!want_ab && !want_cd) return;
+            if (scheme == FB_LIN_FORWARD) { hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_FORWARD, 0>), gd, dim3(256), 0, h->stream, a, o); return; }
+            hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_ONESIDED2, 0>), gd, dim3(256), 0, h->stream, a, o);
+            hipLaunchKernelGGL((k_lin_diff<X, FB_LIN_ONESIDED2, 1>), gd, dim3(256), 0, h->stream, a, o);
+        };
+        if (is_x2(h)) launch(std::true_type{});
+        else launch(std::false_type{});
     }
     HIPCHK(hipGetLastError());
     auto get = [&](double* host, const double* dev, int64_t rows) -> int32_t {

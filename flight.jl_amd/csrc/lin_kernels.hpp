@@ -107,7 +107,7 @@ FBD int32_t lin_eval(const KArgs& a, int64_t i, const Tables& T, const double (&
     int32_t st;
     if constexpr (X) {
         const InputsX in = {&x[X2_ACT], a.u + i, a.n, a.ui[i]};
-        st = rhs<FB_KIN_NED, true, FB_VERB_FAST>(x, a.s[i], a.s[a.n + i], in, env, T, emit, aux, sink);
+        st = rhs<FB_KIN_NED, true>(x, a.s[i], a.s[a.n + i], in, env, T, emit, aux, sink);
 #pragma unroll
         for (int k = 0; k < FB_NACT; k++) xd[X2_ACT + k] = 1 / ACT_TAU * ((k < 4 ? uss[k < 4 ? k : 0] : x2_command(a, i, k)) - x[X2_ACT + k]);
     } else {
@@ -121,7 +121,7 @@ FBD int32_t lin_eval(const KArgs& a, int64_t i, const Tables& T, const double (&
         in.u_glob = a.u + i;
         in.n = a.n;
         in.steer = clampd(clampd(uu[FB_U_RUDDER], -1, 1) + clampd(uu[FB_U_RUDDER_OFFSET], -1, 1), -1, 1);
-        st = rhs<FB_KIN_NED, true, FB_VERB_FAST>(x, a.s[i], a.s[a.n + i], in, env, T, emit, aux, sink);
+        st = rhs<FB_KIN_NED, true>(x, a.s[i], a.s[a.n + i], in, env, T, emit, aux, sink);
     }
     if (wX) {
 #pragma unroll
