@@ -184,7 +184,9 @@ def test_per_aircraft_terrain_elevation_ground_contact(fb, oracle):
 def test_per_aircraft_env_every_stepping_path_agrees(fb, monkeypatch):
     """The rows are read by four stepping kernels in the WA mechanisation: k_step_duo<WA, X, PERENV> (default), k_step_air<WA, X, false, PERENV>
     (FLIGHTBATCH_DUO=0, and FB_F32 handles — the fp32 stepper has no per-aircraft form, such a handle is stepped in fp64) and the ground-capable
-    pass behind each. Same batch, same rows: the paths agree to rounding (they order a few sums differently, like their batch-wide forms)."""
+    pass behind each. Same batch, same rows: the paths agree to rounding (they order a few sums differently, like their batch-wide forms).
+    The instances of the other mechanisations (ECEF, NED), and every one of them against the oracle with lanes in the ground-capable pass:
+    tests/test_gpu_dispatch_matrix.py."""
     K = fb.K
     n = 2048
     tp = lattice_trim_params(fb, n, seed=81)

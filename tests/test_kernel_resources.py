@@ -44,6 +44,19 @@ def test_every_stepping_instance_is_in_the_library(kernels):
     assert "fbf::k_step_f32" in kernels and "fbd::k_trim<false>" in kernels and "fbd::k_trim<true>" in kernels and "fbd::k_scenario<0>" in kernels
 
 
+def test_stepping_instances_are_exactly_the_dispatch_matrix(kernels):
+    """launch_step (csrc/fb_capi.hip) instantiates 12 k_step_duo, 24 k_step_air and the one fp32 stepper: the 37 instances whose table
+    heads tests/test_gpu_dispatch_matrix.py. An instance added to or lost from the dispatcher fails here, without a GPU — and an added one
+    needs a case there."""
+    tf = ("false", "true")
+    want = {f"fbd::k_step_duo<{kin}, {x}, {env}>" for kin in (0, 1, 2) for x in tf for env in tf}
+    want |= {f"fbd::k_step_air<{kin}, {x}, {gnd}, {env}>" for kin in (0, 1, 2) for x in tf for gnd in tf for env in tf}
+    want |= {"fbf::k_step_f32"}
+    assert len(want) == 37
+    have = {name for name in kernels if re.search(r"\bk_step_", name)}
+    assert have == want, f"not in the table: {sorted(have - want)}; missing from the library: {sorted(want - have)}"
+
+
 def test_budgets(kernels):
     for name, k in kernels.items():
         assert k["lds"] <= 160 * 1024, (name, k)
