@@ -285,7 +285,11 @@ static void scn_free(fb_handle h) {
 }
 // every index the kernel will follow is checked HERE, on the host: a table is data from outside, and an out-of-range row on the device is a fault
 static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
-    if (!is_x2(h)) return fail("FB_TABLE_SCENARIO: scenarios drive the Cessna172Xv2's inputs (control-law inputs, vehicle inputs); this handle is another model");
+    // a Cessna172Xv2 or a Cessna172Sv0 whose state rows are doubles; on the second, what only the first has — control-law rows, actuator states — is refused below
+    if (h->model != FB_MODEL_C172X2 && h->model != FB_MODEL_C172S0)
+        return fail("FB_TABLE_SCENARIO: scenarios drive the inputs of a Cessna172Xv2 (control-law inputs, vehicle inputs) or a Cessna172Sv0 (vehicle inputs); this handle is another model family");
+    if (h->dtype != FB_F64)
+        return fail("FB_TABLE_SCENARIO: scenario tables are implemented for FB_F64 handles; this one was created with FB_F32 (its airborne stepper works on float copies of the state rows)");
     if (len < FB_SCN_HDR) return fail("scenario blob: %lld doubles, shorter than its header", (long long)len);
     if (b[0] != 5000001.0) return fail("scenario blob: unknown layout version %g", b[0]);
     auto as_int = [&](double v, int64_t lo, int64_t hi, const char* what, int64_t* out) -> bool {
@@ -298,10 +302,16 @@ static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
     const int64_t need = FB_SCN_HDR + FB_SCN_PHASE_REC * nph + FB_SCN_RULE_REC * nrule + FB_SCN_ACT_REC * nact;
     if (len != need) return fail("scenario blob: %lld doubles given, its header needs %lld", (long long)len, (long long)need);
     const double* PH = b + FB_SCN_HDR; const double* RU = PH + FB_SCN_PHASE_REC * nph; const double* AC = RU + FB_SCN_RULE_REC * nrule;
-    const int nx_dev = (int)FB_X2_NX;
+    const bool ctl = is_x2(h);
+    const int nx_dev = ctl ? (int)FB_X2_NX : (int)FB_NX;   // (device rows: SRC_X reads the model's own state)
+    auto no_ctl = [&](const char* what, const char* where, int64_t idx) {
+        fail("scenario blob: %s %lld addresses control-law rows (%s), which only a Cessna172Xv2 has", where, (long long)idx, what);
+        return false;
+    };
     auto src_ok = [&](double kind, double row, const char* where, int64_t idx) -> bool {
         int64_t k, r;
         if (!as_int(kind, 0, FB_SCN_NSRC - 1, "a source kind", &k)) return false;
+        if (!ctl && (k == FB_SCN_SRC_CS || k == FB_SCN_SRC_CU)) return no_ctl(k == FB_SCN_SRC_CS ? "FB_SCN_SRC_CS" : "FB_SCN_SRC_CU", where, idx);
         const int64_t lim = k == FB_SCN_SRC_X ? nx_dev : k == FB_SCN_SRC_CS ? (int64_t)FB_NCS : k == FB_SCN_SRC_CU ? (int64_t)FB_NCU : k == FB_SCN_SRC_U ? (int64_t)FB_NU :
                             k == FB_SCN_SRC_S ? (int64_t)FB_NS : k == FB_SCN_SRC_PAR ? npar : k == FB_SCN_SRC_REC ? nrec : (int64_t)1 << 30;
         if (!as_int(row, 0, lim - 1, "a source row", &r)) { g_err += std::string(" (") + where + " " + std::to_string(idx) + ")"; return false; }
@@ -325,6 +335,7 @@ static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
         const double* ac = AC + FB_SCN_ACT_REC * k;
         int64_t dst, row, nt, v;
         if (!as_int(ac[0], 0, FB_SCN_NDST - 1, "a destination kind", &dst)) return -1;
+        if (!ctl && dst == FB_SCN_DST_CU) { no_ctl("FB_SCN_DST_CU", "action", k); return -1; }
         const int64_t lim = dst == FB_SCN_DST_CU ? (int64_t)FB_NCU : dst == FB_SCN_DST_U ? (int64_t)FB_NU : dst == FB_SCN_DST_REC ? nrec : (int64_t)1 << 30;
         if (!as_int(ac[1], 0, lim - 1, "a destination row", &row) || !as_int(ac[2], 0, 1, "a wrap flag", &v) || !as_int(ac[4], 0, FB_SCN_NTERM, "a term count", &nt)) return -1;
         for (int64_t t = 0; t < nt; t++) if (!src_ok(ac[5 + 3 * t], ac[6 + 3 * t], "action", k)) return -1;
@@ -351,7 +362,10 @@ static int32_t scn_evaluate(fb_handle h) {
     sc.prog = h->scn_prog; sc.n_ph = h->scn_nph; sc.n_rule = h->scn_nrule; sc.n_act = h->scn_nact; sc.n_par = h->scn_npar; sc.n_rec = h->scn_nrec;
     sc.phase = h->scn_phase; sc.since = h->scn_since; sc.par = h->scn_par; sc.rec = h->scn_rec;
     sc.step = h->steps_done; sc.dt = h->params.dt; sc.t = (double)h->steps_done * h->params.dt;   // sim.t = t_start + nstep dt with t_start = 0 (FC/sim.jl:261-275)
-    with_kin(h, [&](auto KIN) { hipLaunchKernelGGL(k_scenario<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc); });
+    with_model_kin(h, [&](auto X, auto KIN) {
+        if constexpr (X.value) hipLaunchKernelGGL(k_scenario<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+        else hipLaunchKernelGGL(k_scenario_sv0<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -497,6 +511,7 @@ int32_t fb_set_table(fb_handle h, int32_t kind, const void* data, const int64_t*
     HIPCHK(hipStreamSynchronize(h->stream));
     int64_t count = 1;
     for (int k = 0; k < ndims; k++) count *= dims[k];
+    if (kind == FB_TABLE_SCENARIO) return scn_load(h, (const double*)data, ndims == 1 ? dims[0] : -1);   // (says itself which models it serves, and why not the others)
     if ((kind == FB_TABLE_ROBOT2D) != (h->model == FB_MODEL_ROBOT2D)) return fail("table kind does not belong to this model");
     if (kind == FB_TABLE_ROBOT2D) {
         if (count != FB_R2_TABLE_SIZE) return fail("Robot2D blob must hold FB_R2_TABLE_SIZE doubles");
@@ -504,7 +519,6 @@ int32_t fb_set_table(fb_handle h, int32_t kind, const void* data, const int64_t*
         h->r2->have_table = true;
         return 0;
     }
-    if (kind == FB_TABLE_SCENARIO) return scn_load(h, (const double*)data, ndims == 1 ? dims[0] : -1);
     if (kind == FB_TABLE_CTL_GAINS) {
         if (!is_x2(h)) return fail("table kind does not belong to this model");
         const double* b = (const double*)data;

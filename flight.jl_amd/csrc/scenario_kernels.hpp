@@ -1,4 +1,4 @@
-// scenario_kernels.hpp — k_scenario: the device-side `user_callback!` of a batch of Cessna172Xv2.
+// scenario_kernels.hpp — k_scenario / k_scenario_sv0: the device-side `user_callback!` of a batch of Cessna172Xv2 / Cessna172Sv0.
 //
 // Reference: the closures handed to Simulation(...; user_callback!) run after every step, behind f_step! and f_periodic! and ahead of the save
 // (lib/FlightCore/src/sim.jl:185, 204-218, 334-336); the scripted scenarios are such closures — a `phase` symbol, per phase "set these inputs; if
@@ -11,6 +11,11 @@
 // ONE evaluation of f_ode! at the current state with a partial sink (like k_x2_ctl: everything that does not feed the sink is dead code), the
 // control-law record and the discrete states in memory. One lane = one aircraft; lanes of a wave may sit in different phases (the branches are
 // paid once per evaluation, not per stage of a step).
+//
+// user_callback! is model-agnostic (FC/sim.jl:185, 279, 334-336), and the first Cessna172Sv0 demos are scripted input changes on that model
+// (nlsim_q, nlsim_θ: one second from trim, then act.u.elevator += 0.1, c172_demos.jl:108-206): the walk below is ONE device function for both
+// models, instantiated on a traits struct — what a Cessna172Sv0 lacks (control-law rows, actuator states) is compiled out of its instance, and
+// scn_load (fb_capi.hip) refuses a table that names it.
 #pragma once
 #include "c172x_kernels.hpp"
 
@@ -51,9 +56,15 @@ static_assert(FB_SCN_SRC_PSI < FB_SCN_SRC_THETA && FB_SCN_SRC_THETA < FB_SCN_SRC
 // order its semantics prescribe: (A) the `always` actions and the rules, as far as they read nothing of vehicle.y — up to the first rule whose
 // condition does, or the first rule that holds; (B) ONE evaluation for the wave if any of its lanes has stopped at something that reads vehicle.y
 // (a condition, the actions of the rule that fired, `always` actions); (C) the rest of the walk from where (A) stopped.
-template <int KIN>
-__global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
-    __shared__ double dummy_l[8];   // (the partial sink needs none of the staged tables: see k_x2_ctl)
+// The two models an evaluation serves: NX state rows on the device; CTL: the handle has control-law rows (sources CS / CU, destination CU) and its
+// f_ode! takes the surfaces from the actuator states (InputsX) — without, from the inputs u (Inputs, load_inputs)
+struct ScnModelX2 { static constexpr int NX = FB_X2_NX; static constexpr bool CTL = true; };
+struct ScnModelS0 { static constexpr int NX = FB_NX; static constexpr bool CTL = false; };
+
+// (dummy_l: the partial sink needs none of the staged tables, in either model — attitude, velocity, air data and the struts' weight on wheels read
+// the state, the environment and the geoid; everything that reads the aero / engine / propeller tables is dead code: see k_x2_ctl)
+template <class M, int KIN>
+FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     if (a.status[i] != 0) return;   // an aircraft whose simulation has ended gets no callback (FC/sim.jl:561-570)
@@ -77,8 +88,8 @@ __global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
             case FB_SCN_SRC_T: return sc.t;
             case FB_SCN_SRC_T_IN_PHASE: return (double)(sc.step - since) * sc.dt;
             case FB_SCN_SRC_X: return a.x[(int64_t)row * n + i];
-            case FB_SCN_SRC_CS: return a.cs[(int64_t)row * n + i];
-            case FB_SCN_SRC_CU: return cu[(int64_t)row * n + i];
+            case FB_SCN_SRC_CS: if constexpr (M::CTL) return a.cs[(int64_t)row * n + i]; else return 0.0;   // (refused by scn_load on a handle without)
+            case FB_SCN_SRC_CU: if constexpr (M::CTL) return cu[(int64_t)row * n + i]; else return 0.0;
             case FB_SCN_SRC_U: return uu[(int64_t)row * n + i];
             case FB_SCN_SRC_S: return (double)a.s[(int64_t)row * n + i];
             case FB_SCN_SRC_ON_GND: return on_gnd;
@@ -100,7 +111,7 @@ __global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
         for (int k = 0; k < nt; k++) v = v + ac[7 + 3 * k] * source((int)ac[5 + 3 * k], (int)ac[6 + 3 * k]);
         if (ac[2] != 0) v = wrap_to_pi(v);
         const int dst = (int)ac[0], row = (int)ac[1];
-        if (dst == FB_SCN_DST_CU) cu[(int64_t)row * n + i] = v;
+        if (M::CTL && dst == FB_SCN_DST_CU) cu[(int64_t)row * n + i] = v;
         // (an `always` action that assigns what is there already — brakes held, throttle closed, every evaluation of the ground phase — changes nothing:
         // the derivative the steppers carry from launch to launch stays valid)
         else if (dst == FB_SCN_DST_U) { double& r = uu[(int64_t)row * n + i]; if (!(r == v)) { r = v; inputs_changed = true; } }
@@ -147,13 +158,19 @@ __global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
     }
     // ---- (B) vehicle.y at the current state, if any lane of the wave has stopped at something that reads it ----
     if (__builtin_amdgcn_ballot_w64(need) != 0) {
-        const Tables T = {(lds_cptr)dummy_l, a.egm96, (lds_cptr)dummy_l};
-        double x[FB_X2_NX];
+        const Tables T = {dummy_l, a.egm96, dummy_l};
+        double x[M::NX];
 #pragma unroll
-        for (int k = 0; k < FB_X2_NX; k++) x[k] = a.x[(int64_t)k * n + i];
-        const InputsX in = {&x[X2_ACT], a.u + i, n, a.ui[i]};
+        for (int k = 0; k < M::NX; k++) x[k] = a.x[(int64_t)k * n + i];
         StepAux aux;
-        rhs<KIN, true>(x, a.s[i], a.s[n + i], in, env_any(a, i), T, [](int, double) {}, aux, tap);
+        if constexpr (M::CTL) {
+            const InputsX in = {&x[X2_ACT], a.u + i, n, a.ui[i]};
+            rhs<KIN, true>(x, a.s[i], a.s[n + i], in, env_any(a, i), T, [](int, double) {}, aux, tap);
+        } else {
+            Inputs in;
+            load_inputs(a, i, in);
+            rhs<KIN, true>(x, a.s[i], a.s[n + i], in, env_any(a, i), T, [](int, double) {}, aux, tap);
+        }
         on_gnd = aux.wow != 0 ? 1.0 : 0.0;   // is_on_gnd: any strut with weight on wheels (c172.jl:998-1001)
     }
     // ---- (C) the rest of the walk ----
@@ -169,8 +186,22 @@ __global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
         sc.phase[i] = (int)ru[7];
         sc.since[i] = sc.step;
     }
-    // the vehicle's inputs have changed under the derivative the stepping kernels carry from launch to launch
+    // the vehicle's inputs have changed under the derivative the stepping kernels carry from launch to launch (Cessna172Xv2: k1 / k1_valid; a
+    // Cessna172Sv0 handle allocates neither — its steppers evaluate k1 at the start of every launch and rebuild their per-launch constants,
+    // duo_pld, from u in the prologue — so there is nothing to invalidate and the pointer is null)
     if (inputs_changed && a.k1_valid) a.k1_valid[i] = 0;
+}
+
+template <int KIN>
+__global__ __launch_bounds__(256) void k_scenario(KArgs a, ScnArgs sc) {
+    __shared__ double dummy_l[8];
+    scn_walk<ScnModelX2, KIN>(a, sc, (lds_cptr)dummy_l);
+}
+// the Cessna172Sv0 instance: 27 state rows, the surfaces straight from u, no control-law rows
+template <int KIN>
+__global__ __launch_bounds__(256) void k_scenario_sv0(KArgs a, ScnArgs sc) {
+    __shared__ double dummy_l[8];
+    scn_walk<ScnModelS0, KIN>(a, sc, (lds_cptr)dummy_l);
 }
 
 }  // namespace fbd

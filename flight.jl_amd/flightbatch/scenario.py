@@ -17,6 +17,12 @@ Semantics of one evaluation (one aircraft): the `always` actions of its phase ru
 condition holds runs its actions and sets the next phase — at most one transition per evaluation, as in the demos' if / elseif chains.
 Values are read when their action runs, so an action sees what the actions before it wrote.
 
+Models. The reference's callback runs on whatever model the Simulation holds (sim.jl:279), and its first Cessna172Sv0 demos are scripted input
+changes (nlsim_q, nlsim_θ: one second from trim, then `act.u.elevator += 0.1`, c172_demos.jl:108-206). A table loads on a `Cessna172Xv2World` and on
+a `BatchedWorld` (Cessna172Sv0, fp64, any mechanisation); the second has no control-law rows, so cs_ / cu_ sources and cu destinations are refused
+there — by the library when the table is loaded, and by `pack(model="Cessna172Sv0")` before it gets that far. Its scripts write `u(...)`, `ui(...)`
+and `rec(...)` and read T, T_IN_PHASE, x_ (27 rows), u_, s_, ON_GND, H_E, PSI, THETA, PHI, CHI, EAS, CLM, par, rec_.
+
 `evaluate_on_host` is the same interpreter in numpy over arrays the caller supplies: the host-callback form of a table (tests compare the two),
 and the checker's phase machine in tests/test_gpu_scenarios.py (driving the CPU oracle)."""
 from __future__ import annotations
@@ -120,6 +126,16 @@ def cu_(name_or_row) -> Value:
     return _src("CU", K["FB_CU_" + name_or_row] if isinstance(name_or_row, str) else name_or_row)
 
 
+def u_(name_or_row) -> Value:
+    """a row of the vehicle's inputs (FB_U_*): u("ELEVATOR", u_("ELEVATOR") + par(0)) is `act.u.elevator += a`"""
+    return _src("U", K["FB_U_" + name_or_row] if isinstance(name_or_row, str) else name_or_row)
+
+
+def x_(row) -> Value:
+    """a row of the continuous state, in the device's row order (include/flightbatch.h)"""
+    return _src("X", row)
+
+
 def s_(name_or_row) -> Value:
     """a discrete state row (FB_S_STALL, FB_S_ENG_STATE)"""
     return _src("S", K["FB_S_" + name_or_row] if isinstance(name_or_row, str) else name_or_row)
@@ -181,8 +197,19 @@ class Scenario:
     def when(self, phase: int, cond: Condition, actions=(), then: int | None = None):
         self._rules[phase].append((cond, list(actions), phase if then is None else int(then)))
 
-    def pack(self) -> np.ndarray:
-        """the FB_TABLE_SCENARIO blob (include/flightbatch.h)"""
+    def pack(self, model: str | None = None) -> np.ndarray:
+        """the FB_TABLE_SCENARIO blob (include/flightbatch.h). model="Cessna172Sv0": raise on what that model lacks (control-law rows as sources or
+        destinations, state rows past its 27) instead of leaving it to the library; the blob is the same either way."""
+        if model not in (None, "Cessna172Sv0", "Cessna172Xv2"):
+            raise ValueError(f"Scenario.pack: unknown model {model!r}")
+        if model == "Cessna172Sv0":
+            reads = [(c.kind, c.row) for p in self._rules for c, _, _ in p]
+            every = [a for p in self._always for a in p] + [a for p in self._rules for _, ra, _ in p for a in ra]
+            reads += [(k, r) for a in every for k, r, _ in a.value.terms]
+            if any(k in (SRC["CS"], SRC["CU"]) for k, _ in reads) or any(a.dst == DST["CU"] for a in every):
+                raise ValueError("the table addresses control-law rows (cs_ / cu_ sources, cu destinations), which only a Cessna172Xv2 has")
+            if any(k == SRC["X"] and not 0 <= r < K["FB_NX"] for k, r in reads):
+                raise ValueError(f"a Cessna172Sv0 has {K['FB_NX']} state rows")
         acts: list[Action] = []
         rules, phases = [], []
         for p in range(len(self.names)):
@@ -218,7 +245,8 @@ def _wrap(x):
 
 def evaluate_on_host(blob: np.ndarray, st: dict, t: float, dt: float) -> None:
     """One evaluation of the table for every aircraft, in place. st: phase [n] int, since [n] int64 (step count at the entry of the phase),
-    step (int: steps taken), par [n_par, n], rec [n_rec, n], cu, cs, u, ui, s (the model's arrays, modified in place), and the outputs the
+    step (int: steps taken), par [n_par, n], rec [n_rec, n], cu, cs, u, ui, s (the model's arrays, modified in place; cu and cs only where the table
+    names them — a Cessna172Sv0's dict has neither), and the outputs the
     sources name: on_gnd, h_e, psi, theta, phi, chi, EAS, clm [n]; x [rows, n] (device row order) where SRC X is used; active [n] bool
     (aircraft whose simulation has ended are not evaluated)."""
     assert blob[0] == MAGIC

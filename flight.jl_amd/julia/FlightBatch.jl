@@ -285,6 +285,9 @@ Base.getproperty(sim::BatchedSimulation, s::Symbol) = s === :t ? getfield(sim, :
 # (FlightApps/demos/c172_demos.jl:423-486, 525-642: a phase symbol, per phase "set these inputs; if <condition> set those, next phase") are
 # a table of phases, rules and actions that a kernel interprets between the stepping launches. `blob` is the packed table (the layout is in
 # the header; flightbatch/scenario.py builds it on the Python side), `par` the per-aircraft parameter rows [N x n_par].
+# The callback is model-agnostic in the reference (FC/sim.jl:279), and so are these verbs: a Cessna172Xv2 world takes every source and
+# destination; a Cessna172Sv0 world (fp64, any mechanisation) takes tables that write the vehicle's inputs and records — the nlsim_q / nlsim_θ
+# elevator step, c172_demos.jl:108-206 — and the library refuses control-law rows (sources CS / CU, destination CU) on it, with the reason.
 const TABLE_SCENARIO = Cint(6)
 function set_scenario!(w::BatchedWorld, blob::Vector{Float64}, par::Union{Matrix{Float64}, Nothing} = nothing; every::Integer = 1)
     len = Ref{Int64}(length(blob))

@@ -218,7 +218,7 @@ enum {
     FB_TABLE_AERO = 3,      /* packed blob, layout in csrc/tables.h; FA/c172/c172.jl:51-199 */
     FB_TABLE_ROBOT2D = 4,   /* FB_R2_TABLE_SIZE doubles, see above; FA/robot2d/robot2d.jl:20-30,419-436 */
     FB_TABLE_CTL_GAINS = 5, /* Cessna172Xv2 autopilot gain lookups, layout above; FP/control.jl:879-994 */
-    FB_TABLE_SCENARIO = 6   /* Cessna172Xv2: a scripted scenario as a table (below): the device-side user_callback!; FC/sim.jl:185, 334-336 */
+    FB_TABLE_SCENARIO = 6   /* Cessna172Xv2, Cessna172Sv0 (FB_F64): a scripted scenario as a table (below): the device-side user_callback!; FC/sim.jl:185, 334-336 */
 };
 
 /* World-level parameters shared by the whole batch (one SimpleWorld each in the reference, identical here) */
@@ -404,7 +404,7 @@ int32_t fb_get_step_count(fb_handle h, int64_t* count);
 int32_t fb_set_step_count(fb_handle h, int64_t count, double t);
 int32_t fb_set_status(fb_handle h, const int32_t* status);
 
-/* ---- Scripted scenarios: `user_callback!` on the device (Cessna172Xv2) -------------------------------------------------------------
+/* ---- Scripted scenarios: `user_callback!` on the device (Cessna172Xv2, Cessna172Sv0 in fp64) ----------------------------------------
  * The reference's scenarios are closures that run after every step, behind f_step! / f_periodic! and ahead of the save (FC/sim.jl:185,
  * 204-218, 334-336): a phase symbol and, per phase, "set these inputs; if <condition on the model's outputs> set those and go on to the next
  * phase" (FA demos/c172_demos.jl:423-486 crosswind landing, :525-642 traffic pattern). For a batch the same logic is a TABLE, interpreted per
@@ -424,7 +424,12 @@ int32_t fb_set_status(fb_handle h, const int32_t* status);
  *                                       and clears them otherwise. A value is read when its action runs (it sees the actions before it).
  * Sources: FB_SCN_SRC_T = sim.t behind the step (steps taken x dt), T_IN_PHASE = (steps taken - step of entry) x dt, X / CS / CU / U / S = rows of
  * the state (device row order) / control-law record / control-law inputs / vehicle inputs / discrete states, PAR / REC = the aircraft's own rows,
- * and of vehicle.y at the current state: ON_GND (is_on_gnd, 0 / 1; c172.jl:998-1001), H_E, PSI / THETA / PHI (e_nb), CHI, EAS, CLM (climb rate). */
+ * and of vehicle.y at the current state: ON_GND (is_on_gnd, 0 / 1; c172.jl:998-1001), H_E, PSI / THETA / PHI (e_nb), CHI, EAS, CLM (climb rate).
+ * Models: user_callback! is model-agnostic in the reference (FC/sim.jl:279), and so is the table, with what a model lacks refused when it is
+ * loaded. A Cessna172Xv2 handle takes every source and destination, FB_SCN_SRC_X rows < FB_X2_NX. A Cessna172Sv0 handle created with FB_F64
+ * (any mechanisation, with or without fb_set_env rows) has no control-law rows: FB_SCN_SRC_CS, FB_SCN_SRC_CU and FB_SCN_DST_CU are refused,
+ * FB_SCN_SRC_X rows < FB_NX; its scripts write the vehicle's inputs (FB_SCN_DST_U, _UI: `act.u.elevator += 0.1`, c172_demos.jl:108-206) and
+ * records. FB_F32 handles and Robot2D refuse the table. */
 enum { FB_SCN_HDR = 8, FB_SCN_PHASE_REC = 4, FB_SCN_RULE_REC = 8, FB_SCN_ACT_REC = 14, FB_SCN_NTERM = 3 };
 enum { FB_SCN_SRC_CONST = 0, FB_SCN_SRC_T, FB_SCN_SRC_T_IN_PHASE, FB_SCN_SRC_X, FB_SCN_SRC_CS, FB_SCN_SRC_CU, FB_SCN_SRC_U, FB_SCN_SRC_S,
        FB_SCN_SRC_ON_GND, FB_SCN_SRC_H_E, FB_SCN_SRC_PSI, FB_SCN_SRC_THETA, FB_SCN_SRC_PHI, FB_SCN_SRC_CHI, FB_SCN_SRC_EAS, FB_SCN_SRC_CLM,
