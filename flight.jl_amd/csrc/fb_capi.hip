@@ -88,6 +88,7 @@ struct fb_handle_s {
     // scripted scenario (FB_TABLE_SCENARIO): the program blob and the per-aircraft rows, all in device memory
     double* scn_prog = nullptr; int scn_nph = 0, scn_nrule = 0, scn_nact = 0, scn_npar = 0, scn_nrec = 0, scn_every = 0;
     int32_t* scn_phase = nullptr; long long* scn_since = nullptr; double* scn_par = nullptr; double* scn_rec = nullptr;
+    bool scn_env = false, scn_y = false;   // the loaded table names FB_SCN_SRC_ENV / FB_SCN_DST_ENV (the rows must stay); FB_SCN_SRC_Y (fb_step refreshes y ahead of an evaluation)
     // fb_linearize / fb_linearize_state: device rows of the results (ẋ0 x0 u0 y0 | A B | C D) and the status OR, kept and grown on demand
     double* lin_buf = nullptr; size_t lin_doubles = 0; int32_t* lin_st = nullptr;
 };
@@ -282,6 +283,7 @@ static void scn_free(fb_handle h) {
     hipFree(h->scn_prog); hipFree(h->scn_phase); hipFree(h->scn_since); hipFree(h->scn_par); hipFree(h->scn_rec);
     h->scn_prog = nullptr; h->scn_phase = nullptr; h->scn_since = nullptr; h->scn_par = nullptr; h->scn_rec = nullptr;
     h->scn_nph = h->scn_nrule = h->scn_nact = h->scn_npar = h->scn_nrec = h->scn_every = 0;
+    h->scn_env = h->scn_y = false;
 }
 // every index the kernel will follow is checked HERE, on the host: a table is data from outside, and an out-of-range row on the device is a fault
 static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
@@ -308,12 +310,23 @@ static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
         fail("scenario blob: %s %lld addresses control-law rows (%s), which only a Cessna172Xv2 has", where, (long long)idx, what);
         return false;
     };
+    bool uses_env = false, uses_y = false;
+    // the world's rows exist only on a handle that carries them: fb_set_env first
+    auto env_rows_ok = [&](const char* what, const char* where, int64_t idx) {
+        uses_env = true;
+        if (h->env_rows) return true;
+        fail("scenario blob: %s %lld addresses the aircraft's environment rows (%s), and this handle has none: set them with fb_set_env before the table is loaded", where, (long long)idx, what);
+        return false;
+    };
     auto src_ok = [&](double kind, double row, const char* where, int64_t idx) -> bool {
         int64_t k, r;
         if (!as_int(kind, 0, FB_SCN_NSRC - 1, "a source kind", &k)) return false;
+        if (k == FB_SCN_SRC_ENV && !env_rows_ok("FB_SCN_SRC_ENV", where, idx)) return false;
+        if (k == FB_SCN_SRC_Y) uses_y = true;
         if (!ctl && (k == FB_SCN_SRC_CS || k == FB_SCN_SRC_CU)) return no_ctl(k == FB_SCN_SRC_CS ? "FB_SCN_SRC_CS" : "FB_SCN_SRC_CU", where, idx);
         const int64_t lim = k == FB_SCN_SRC_X ? nx_dev : k == FB_SCN_SRC_CS ? (int64_t)FB_NCS : k == FB_SCN_SRC_CU ? (int64_t)FB_NCU : k == FB_SCN_SRC_U ? (int64_t)FB_NU :
-                            k == FB_SCN_SRC_S ? (int64_t)FB_NS : k == FB_SCN_SRC_PAR ? npar : k == FB_SCN_SRC_REC ? nrec : (int64_t)1 << 30;
+                            k == FB_SCN_SRC_S ? (int64_t)FB_NS : k == FB_SCN_SRC_PAR ? npar : k == FB_SCN_SRC_REC ? nrec : k == FB_SCN_SRC_ENV ? (int64_t)FB_NENV :
+                            k == FB_SCN_SRC_Y ? (int64_t)FB_NY : (int64_t)1 << 30;
         if (!as_int(row, 0, lim - 1, "a source row", &r)) { g_err += std::string(" (") + where + " " + std::to_string(idx) + ")"; return false; }
         return true;
     };
@@ -336,24 +349,43 @@ static int32_t scn_load(fb_handle h, const double* b, int64_t len) {
         int64_t dst, row, nt, v;
         if (!as_int(ac[0], 0, FB_SCN_NDST - 1, "a destination kind", &dst)) return -1;
         if (!ctl && dst == FB_SCN_DST_CU) { no_ctl("FB_SCN_DST_CU", "action", k); return -1; }
-        const int64_t lim = dst == FB_SCN_DST_CU ? (int64_t)FB_NCU : dst == FB_SCN_DST_U ? (int64_t)FB_NU : dst == FB_SCN_DST_REC ? nrec : (int64_t)1 << 30;
-        if (!as_int(ac[1], 0, lim - 1, "a destination row", &row) || !as_int(ac[2], 0, 1, "a wrap flag", &v) || !as_int(ac[4], 0, FB_SCN_NTERM, "a term count", &nt)) return -1;
+        if (dst == FB_SCN_DST_ENV && !env_rows_ok("FB_SCN_DST_ENV", "action", k)) return -1;
+        const int64_t lim = dst == FB_SCN_DST_CU ? (int64_t)FB_NCU : dst == FB_SCN_DST_U ? (int64_t)FB_NU : dst == FB_SCN_DST_REC ? nrec :
+                            dst == FB_SCN_DST_ENV ? (int64_t)FB_NENV : (int64_t)1 << 30;
+        if (!as_int(ac[1], 0, lim - 1, "a destination row", &row)) return -1;
+        if (dst == FB_SCN_DST_ENV && (row == FB_ENV_T_SL || row == FB_ENV_P_SL))
+            return fail("scenario blob: action %lld writes FB_ENV_%s: a sea-level row carries two derived rows that fb_set_env fills with the host's log / exp / sqrt, "
+                        "which a write on the device could not reproduce bit for bit; a table writes FB_ENV_WIND_N / _E / _D only", (long long)k, row == FB_ENV_T_SL ? "T_SL" : "P_SL");
+        if (dst == FB_SCN_DST_ENV && row == FB_ENV_H_TERRAIN)
+            return fail("scenario blob: action %lld writes FB_ENV_H_TERRAIN: the terrain elevation is a constructor argument of HorizontalTerrain in the reference, "
+                        "not an input; a table writes FB_ENV_WIND_N / _E / _D only", (long long)k);
+        if (!as_int(ac[2], 0, 1, "a wrap flag", &v) || !as_int(ac[4], 0, FB_SCN_NTERM, "a term count", &nt)) return -1;
         for (int64_t t = 0; t < nt; t++) if (!src_ok(ac[5 + 3 * t], ac[6 + 3 * t], "action", k)) return -1;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    scn_free(h);
+    // everything is allocated and filled into locals and committed to the handle only when all of it has succeeded: a failure on the way leaves
+    // the handle with the table it had (or none), never with half of a new one
     const int64_t n = h->n;
-    HIPCHK(hipMalloc(&h->scn_prog, sizeof(double) * len));
-    HIPCHK(hipMemcpy(h->scn_prog, b, sizeof(double) * len, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->scn_phase, sizeof(int32_t) * n));
-    HIPCHK(hipMalloc(&h->scn_since, sizeof(long long) * n));
-    HIPCHK(hipMalloc(&h->scn_par, sizeof(double) * (npar > 0 ? npar : 1) * n));
-    HIPCHK(hipMalloc(&h->scn_rec, sizeof(double) * (nrec > 0 ? nrec : 1) * n));
-    HIPCHK(hipMemset(h->scn_phase, 0, sizeof(int32_t) * n));
-    HIPCHK(hipMemset(h->scn_since, 0, sizeof(long long) * n));
-    HIPCHK(hipMemset(h->scn_par, 0, sizeof(double) * (npar > 0 ? npar : 1) * n));
-    HIPCHK(hipMemset(h->scn_rec, 0, sizeof(double) * (nrec > 0 ? nrec : 1) * n));
+    struct Rows {
+        double* prog = nullptr; int32_t* phase = nullptr; long long* since = nullptr; double* par = nullptr; double* rec = nullptr;
+        ~Rows() { (void)hipFree(prog); (void)hipFree(phase); (void)hipFree(since); (void)hipFree(par); (void)hipFree(rec); }
+    } R;
+    const size_t par_bytes = sizeof(double) * (npar > 0 ? npar : 1) * n, rec_bytes = sizeof(double) * (nrec > 0 ? nrec : 1) * n;
+    HIPCHK(hipMalloc(&R.prog, sizeof(double) * len));
+    HIPCHK(hipMemcpy(R.prog, b, sizeof(double) * len, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&R.phase, sizeof(int32_t) * n));
+    HIPCHK(hipMalloc(&R.since, sizeof(long long) * n));
+    HIPCHK(hipMalloc(&R.par, par_bytes));
+    HIPCHK(hipMalloc(&R.rec, rec_bytes));
+    HIPCHK(hipMemset(R.phase, 0, sizeof(int32_t) * n));
+    HIPCHK(hipMemset(R.since, 0, sizeof(long long) * n));
+    HIPCHK(hipMemset(R.par, 0, par_bytes));
+    HIPCHK(hipMemset(R.rec, 0, rec_bytes));
+    scn_free(h);
+    h->scn_prog = R.prog; h->scn_phase = R.phase; h->scn_since = R.since; h->scn_par = R.par; h->scn_rec = R.rec;
+    R.prog = nullptr; R.phase = nullptr; R.since = nullptr; R.par = nullptr; R.rec = nullptr;   // (the handle owns them now)
     h->scn_nph = (int)nph; h->scn_nrule = (int)nrule; h->scn_nact = (int)nact; h->scn_npar = (int)npar; h->scn_nrec = (int)nrec; h->scn_every = 1;
+    h->scn_env = uses_env; h->scn_y = uses_y;
     return 0;
 }
 // one evaluation of the table for every aircraft, behind the step that has just completed (steps_done counts it)
@@ -362,9 +394,22 @@ static int32_t scn_evaluate(fb_handle h) {
     sc.prog = h->scn_prog; sc.n_ph = h->scn_nph; sc.n_rule = h->scn_nrule; sc.n_act = h->scn_nact; sc.n_par = h->scn_npar; sc.n_rec = h->scn_nrec;
     sc.phase = h->scn_phase; sc.since = h->scn_since; sc.par = h->scn_par; sc.rec = h->scn_rec;
     sc.step = h->steps_done; sc.dt = h->params.dt; sc.t = (double)h->steps_done * h->params.dt;   // sim.t = t_start + nstep dt with t_start = 0 (FC/sim.jl:261-275)
+    // a table that reads rows of mdl.y: the full record at the state behind the step, by the evaluation the device log runs at a save instant
+    // (fb_f_ode allocates the record on its first call; like every fb_f_ode, it marks an aircraft whose state throws: FB_TERM_OUTSIDE_STEP)
+    if (h->scn_y) {
+        if (int32_t rc = fb_f_ode(h, nullptr)) return rc;
+        h->launches++;
+    }
+    sc.y = h->y;
+    const bool world = h->scn_env || h->scn_y;   // (the instance with the world's kinds only for a table that names one: older tables run the code they always ran)
     with_model_kin(h, [&](auto X, auto KIN) {
-        if constexpr (X.value) hipLaunchKernelGGL(k_scenario<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
-        else hipLaunchKernelGGL(k_scenario_sv0<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+        if constexpr (X.value) {
+            if (world) hipLaunchKernelGGL(k_scenario_world<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+            else hipLaunchKernelGGL(k_scenario<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+        } else {
+            if (world) hipLaunchKernelGGL(k_scenario_sv0_world<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+            else hipLaunchKernelGGL(k_scenario_sv0<KIN.value>, grid_for(h->n, 256), dim3(256), 0, h->stream, make_args(h), sc);
+        }
     });
     HIPCHK(hipGetLastError());
     return 0;
@@ -606,6 +651,9 @@ int32_t fb_set_env(fb_handle h, const double* env) {
     fsal_invalidate(h);
     HIPCHK(hipSetDevice(h->device));
     if (!env) {
+        if (h->scn_env)
+            return fail("fb_set_env(NULL): the loaded scenario table reads or writes the aircraft's environment rows (FB_SCN_SRC_ENV / FB_SCN_DST_ENV), which fb_set_env "
+                        "has set; switch the scenario off first (fb_scenario_configure(h, 0))");
         HIPCHK(hipStreamSynchronize(h->stream));
         hipFree(h->env_rows);
         h->env_rows = nullptr;

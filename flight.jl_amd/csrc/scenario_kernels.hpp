@@ -16,6 +16,11 @@
 // (nlsim_q, nlsim_θ: one second from trim, then act.u.elevator += 0.1, c172_demos.jl:108-206): the walk below is ONE device function for both
 // models, instantiated on a traits struct — what a Cessna172Sv0 lacks (control-law rows, actuator states) is compiled out of its instance, and
 // scn_load (fb_capi.hip) refuses a table that names it.
+//
+// The world: the reference's scripts also write world.atmosphere.wind.u (c172_demos.jl:225-228, 427-433) — here the aircraft's own rows of
+// KArgs::env_rows (FB_SCN_SRC_ENV / FB_SCN_DST_ENV; scn_load wants the rows set and lets only the three wind rows be written) — and may read any
+// field of mdl.y: FB_SCN_SRC_Y is a row of the full output record, which fb_step refreshes (k_f_ode) ahead of the evaluation of a table that
+// names the kind. The partial sink below stays as narrow as it is: a row chosen at run time would keep the whole of rhs() live in this kernel.
 #pragma once
 #include "c172x_kernels.hpp"
 
@@ -30,6 +35,7 @@ struct ScnArgs {
     double* rec;             // [n_rec x n]
     long long step;          // steps taken since init (this evaluation stands behind step number `step`)
     double t, dt;
+    const double* y;         // [FB_NY x n] the output record, refreshed by fb_step ahead of this evaluation when the table names FB_SCN_SRC_Y (else unused)
 };
 
 // the outputs a scenario may read, tapped from rhs() (rows of the output record, include/flightbatch.h FB_Y_*)
@@ -63,7 +69,9 @@ struct ScnModelS0 { static constexpr int NX = FB_NX; static constexpr bool CTL =
 
 // (dummy_l: the partial sink needs none of the staged tables, in either model — attitude, velocity, air data and the struts' weight on wheels read
 // the state, the environment and the geoid; everything that reads the aero / engine / propeller tables is dead code: see k_x2_ctl)
-template <class M, int KIN>
+// WORLD: the walk with the world's kinds (FB_SCN_SRC_ENV / _DST_ENV / FB_SCN_SRC_Y) compiled in. fb_step launches that instance only for a table that names
+// one of them (scn_load knows), so every older table runs the code it ran before these kinds existed.
+template <class M, int KIN, bool WORLD = false>
 FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
@@ -74,6 +82,7 @@ FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
     double* const cu = const_cast<double*>(a.cu);
     double* const uu = const_cast<double*>(a.u);
     int32_t* const uiw = const_cast<int32_t*>(a.ui);
+    [[maybe_unused]] double* const env = const_cast<double*>(a.env_rows);   // (null on a handle without rows: scn_load has refused a table that names them)
     const double* PH = sc.prog + FB_SCN_HDR;
     const double* RU = PH + FB_SCN_PHASE_REC * sc.n_ph;
     const double* AC = RU + FB_SCN_RULE_REC * sc.n_rule;
@@ -102,6 +111,8 @@ FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
             case FB_SCN_SRC_CLM: return -tap.vd;
             case FB_SCN_SRC_PAR: return sc.par[(int64_t)row * n + i];
             case FB_SCN_SRC_REC: return sc.rec[(int64_t)row * n + i];
+            case FB_SCN_SRC_ENV: if constexpr (WORLD) return env[(int64_t)row * n + i]; else return 0.0;
+            case FB_SCN_SRC_Y: if constexpr (WORLD) return sc.y[(int64_t)row * n + i]; else return 0.0;   // (nothing here writes the record: read "before any action" whenever it is read)
         }
         return 0.0;
     };
@@ -116,6 +127,9 @@ FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
         // the derivative the steppers carry from launch to launch stays valid)
         else if (dst == FB_SCN_DST_U) { double& r = uu[(int64_t)row * n + i]; if (!(r == v)) { r = v; inputs_changed = true; } }
         else if (dst == FB_SCN_DST_REC) sc.rec[(int64_t)row * n + i] = v;
+        // (a wind row, like an input: written where it differs, and then the carried derivative is stale; written ahead of stage (B), it is what
+        // (B)'s f_ode! sees — env_any reads the rows there)
+        else if (WORLD && dst == FB_SCN_DST_ENV) { double& r = env[(int64_t)row * n + i]; if (!(r == v)) { r = v; inputs_changed = true; } }
         else if (dst == FB_SCN_DST_UI) { const int w = uiw[i], w1 = v != 0 ? (w | row) : (w & ~row); if (w1 != w) { uiw[i] = w1; inputs_changed = true; } }
     };
     auto acts_need_y = [&](int first, int count) {
@@ -186,7 +200,7 @@ FBD void scn_walk(const KArgs& a, const ScnArgs& sc, lds_cptr dummy_l) {
         sc.phase[i] = (int)ru[7];
         sc.since[i] = sc.step;
     }
-    // the vehicle's inputs have changed under the derivative the stepping kernels carry from launch to launch (Cessna172Xv2: k1 / k1_valid; a
+    // the vehicle's inputs or its wind have changed under the derivative the stepping kernels carry from launch to launch (Cessna172Xv2: k1 / k1_valid; a
     // Cessna172Sv0 handle allocates neither — its steppers evaluate k1 at the start of every launch and rebuild their per-launch constants,
     // duo_pld, from u in the prologue — so there is nothing to invalidate and the pointer is null)
     if (inputs_changed && a.k1_valid) a.k1_valid[i] = 0;
@@ -202,6 +216,18 @@ template <int KIN>
 __global__ __launch_bounds__(256) void k_scenario_sv0(KArgs a, ScnArgs sc) {
     __shared__ double dummy_l[8];
     scn_walk<ScnModelS0, KIN>(a, sc, (lds_cptr)dummy_l);
+}
+
+// the instances for a table that names the world's kinds
+template <int KIN>
+__global__ __launch_bounds__(256) void k_scenario_world(KArgs a, ScnArgs sc) {
+    __shared__ double dummy_l[8];
+    scn_walk<ScnModelX2, KIN, true>(a, sc, (lds_cptr)dummy_l);
+}
+template <int KIN>
+__global__ __launch_bounds__(256) void k_scenario_sv0_world(KArgs a, ScnArgs sc) {
+    __shared__ double dummy_l[8];
+    scn_walk<ScnModelS0, KIN, true>(a, sc, (lds_cptr)dummy_l);
 }
 
 }  // namespace fbd

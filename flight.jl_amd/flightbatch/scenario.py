@@ -23,8 +23,15 @@ a `BatchedWorld` (Cessna172Sv0, fp64, any mechanisation); the second has no cont
 there — by the library when the table is loaded, and by `pack(model="Cessna172Sv0")` before it gets that far. Its scripts write `u(...)`, `ui(...)`
 and `rec(...)` and read T, T_IN_PHASE, x_ (27 rows), u_, s_, ON_GND, H_E, PSI, THETA, PHI, CHI, EAS, CLM, par, rec_.
 
+The world. The reference's scripts set `world.atmosphere.wind.u.N / .E` as well (c172_demos.jl:225-228, 427-433) and may read anything in `mdl.y`
+(sim.jl:185, 279, 334-336). On a world whose per-aircraft environment rows are set (`set_env`), `env_("WIND_E")` reads the aircraft's own row (all six
+FB_ENV_* rows) and `env("WIND_E", value)` writes its wind (the three wind rows only: the sea-level rows carry derived rows only the host computes, the
+terrain elevation is a constructor argument in the reference); `y_(row)` reads any row of the output record at the state behind the step — the device
+then refreshes the whole record ahead of every evaluation, one `f_ode!` pass that a table without `y_` does not pay.
+
 `evaluate_on_host` is the same interpreter in numpy over arrays the caller supplies: the host-callback form of a table (tests compare the two),
-and the checker's phase machine in tests/test_gpu_scenarios.py (driving the CPU oracle)."""
+and the checker's phase machine in tests/test_gpu_scenarios.py (driving the CPU oracle). `host_callback` wraps it as the `user_callback` of a
+Simulation: the model's arrays down, one evaluation, what changed back up."""
 from __future__ import annotations
 
 import numpy as np
@@ -35,8 +42,10 @@ MAGIC = 5.0e6 + 1   # version 1 of the blob layout
 HDR, PH_REC, RULE_REC, ACT_REC, NTERM = 8, 4, 8, 14, 3
 # value sources (kind, row)
 SRC = {name: K["FB_SCN_SRC_" + name] for name in ("CONST", "T", "T_IN_PHASE", "X", "CS", "CU", "U", "S", "ON_GND", "H_E", "PSI", "THETA", "PHI", "CHI",
-                                                     "EAS", "CLM", "PAR", "REC")}
-DST = {name: K["FB_SCN_DST_" + name] for name in ("CU", "U", "UI", "REC")}
+                                                     "EAS", "CLM", "PAR", "REC", "ENV", "Y")}
+DST = {name: K["FB_SCN_DST_" + name] for name in ("CU", "U", "UI", "REC", "ENV")}
+WIND_ROWS = (K["FB_ENV_WIND_N"], K["FB_ENV_WIND_E"], K["FB_ENV_WIND_D"])
+TAPPED = tuple(SRC[k] for k in ("ON_GND", "H_E", "PSI", "THETA", "PHI", "CHI", "EAS", "CLM"))
 CMP = {"<": K["FB_SCN_LT"], ">": K["FB_SCN_GT"], ">=": K["FB_SCN_GE"], "<=": K["FB_SCN_LE"], "==": K["FB_SCN_EQ"], "!=": K["FB_SCN_NE"], "always": K["FB_SCN_ALWAYS"]}
 
 
@@ -141,6 +150,20 @@ def s_(name_or_row) -> Value:
     return _src("S", K["FB_S_" + name_or_row] if isinstance(name_or_row, str) else name_or_row)
 
 
+def _env_row(name_or_row) -> int:
+    return K["FB_ENV_" + name_or_row] if isinstance(name_or_row, str) else int(name_or_row)
+
+
+def env_(name_or_row) -> Value:
+    """a row of the aircraft's own environment (FB_ENV_*: env_("WIND_E"), env_("H_TERRAIN")), as world.env holds it; the world needs rows (set_env)"""
+    return _src("ENV", _env_row(name_or_row))
+
+
+def y_(row) -> Value:
+    """a row of the output record mdl.y at the state behind the step (include/flightbatch.h FB_Y_*: y_(K["FB_Y_AIR"] + 19) is the TAS)"""
+    return _src("Y", K[row] if isinstance(row, str) else row)
+
+
 def par(row) -> Value:
     return _src("PAR", row)
 
@@ -173,6 +196,11 @@ def ui(bit_name, on) -> Action:
 def rec(row, value) -> Action:
     """record slot `row` of the aircraft = value (touchdown time, position ...: read back with world.scenario_state())"""
     return Action(DST["REC"], row, value)
+
+
+def env(name, value) -> Action:
+    """world.atmosphere.wind.u.<N / E / D> = value for this aircraft (FB_ENV_WIND_N / _E / _D; the other environment rows are refused by pack)"""
+    return Action(DST["ENV"], _env_row(name), value)
 
 
 def target(p1_par: int, p2_par: int):
@@ -210,6 +238,25 @@ class Scenario:
                 raise ValueError("the table addresses control-law rows (cs_ / cu_ sources, cu destinations), which only a Cessna172Xv2 has")
             if any(k == SRC["X"] and not 0 <= r < K["FB_NX"] for k, r in reads):
                 raise ValueError(f"a Cessna172Sv0 has {K['FB_NX']} state rows")
+        all_reads = [(c.kind, c.row) for p in self._rules for c, _, _ in p]
+        all_acts = [a for p in self._always for a in p] + [a for p in self._rules for _, ra, _ in p for a in ra]
+        all_reads += [(k, r) for a in all_acts for k, r, _ in a.value.terms]
+        for k, r in all_reads:   # (what the library refuses when the table is loaded, whatever the model)
+            if k == SRC["ENV"] and not 0 <= r < K["FB_NENV"]:
+                raise ValueError(f"environment row out of range: the rows are FB_ENV_* (0 .. {K['FB_NENV'] - 1})")
+            if k == SRC["Y"] and not 0 <= r < K["FB_NY"]:
+                raise ValueError(f"output row out of range: the output record has {K['FB_NY']} rows")
+        for a in all_acts:
+            if a.dst != DST["ENV"]:
+                continue
+            if a.row in (K["FB_ENV_T_SL"], K["FB_ENV_P_SL"]):
+                raise ValueError("a table cannot write the sea-level rows (T_SL, P_SL): each carries derived rows the host fills with its own log / exp / sqrt "
+                                 "(set_env), which a device write could not reproduce; a table writes WIND_N / WIND_E / WIND_D")
+            if a.row == K["FB_ENV_H_TERRAIN"]:
+                raise ValueError("a table cannot write H_TERRAIN: the terrain elevation is a constructor argument of HorizontalTerrain in the reference, not an "
+                                 "input; a table writes WIND_N / WIND_E / WIND_D")
+            if a.row not in WIND_ROWS:
+                raise ValueError("environment destination row out of range: a table writes WIND_N / WIND_E / WIND_D")
         acts: list[Action] = []
         rules, phases = [], []
         for p in range(len(self.names)):
@@ -248,7 +295,15 @@ def evaluate_on_host(blob: np.ndarray, st: dict, t: float, dt: float) -> None:
     step (int: steps taken), par [n_par, n], rec [n_rec, n], cu, cs, u, ui, s (the model's arrays, modified in place; cu and cs only where the table
     names them — a Cessna172Sv0's dict has neither), and the outputs the
     sources name: on_gnd, h_e, psi, theta, phi, chi, EAS, clm [n]; x [rows, n] (device row order) where SRC X is used; active [n] bool
-    (aircraft whose simulation has ended are not evaluated)."""
+    (aircraft whose simulation has ended are not evaluated). The world's kinds: env [FB_NENV, n] (the rows of world.env) where the table names
+    SRC / DST ENV — a wind row is written only where the value differs, and st["env_changed"] [n] bool is set (or OR-ed into) for those aircraft;
+    y [FB_NY, n] (the output record at the state behind the step) where it names SRC Y — no action writes it, so it is the record as it stood when
+    the evaluation began, also behind a wind write.
+    The tapped outputs behind a wind write: on the device the `always` actions of a phase that read no tapped output run AHEAD of the evaluation of
+    f_ode! the taps come from (stage A, then B: csrc/scenario_kernels.hpp), so a rule on EAS — the one tap that depends on the wind — sees the wind such
+    an action has just written, while y_(FB_Y_AIR + 20) is the record's EAS from before it. The same order here: those `always` actions first, for every
+    phase; then, if one of them changed a wind row and the caller gave st["retap"], retap(st) is called to renew the tapped entries of st under the new
+    rows (host_callback: set_env, f_ode!, fetch); then the other `always` actions and the rules. Without `retap` the tapped entries stay as supplied."""
     assert blob[0] == MAGIC
     n_ph, n_rule, n_act = int(blob[1]), int(blob[2]), int(blob[3])
     PH = blob[HDR:HDR + PH_REC * n_ph].reshape(n_ph, PH_REC)
@@ -269,6 +324,8 @@ def evaluate_on_host(blob: np.ndarray, st: dict, t: float, dt: float) -> None:
         if kind == SRC["S"]: return st["s"][row, m].astype(np.float64)
         if kind == SRC["PAR"]: return st["par"][row, m]
         if kind == SRC["REC"]: return st["rec"][row, m]
+        if kind == SRC["ENV"]: return st["env"][row, m]
+        if kind == SRC["Y"]: return st["y"][row, m]
         name = {SRC["ON_GND"]: "on_gnd", SRC["H_E"]: "h_e", SRC["PSI"]: "psi", SRC["THETA"]: "theta", SRC["PHI"]: "phi", SRC["CHI"]: "chi",
                 SRC["EAS"]: "EAS", SRC["CLM"]: "clm"}[kind]
         return np.asarray(st[name], dtype=np.float64)[m]
@@ -286,17 +343,35 @@ def evaluate_on_host(blob: np.ndarray, st: dict, t: float, dt: float) -> None:
         if dst == DST["CU"]: st["cu"][row, m] = v
         elif dst == DST["U"]: st["u"][row, m] = v
         elif dst == DST["REC"]: st["rec"][row, m] = v
+        elif dst == DST["ENV"]:
+            differs = ~(st["env"][row, m] == v)   # (like the device: a wind row is written only where the value differs)
+            idx = np.flatnonzero(m)[differs]
+            st["env"][row, idx] = v[differs]
+            st.setdefault("env_changed", np.zeros(n, bool))[idx] = True
         else:
             w = st["ui"][m]
             st["ui"][m] = np.where(v != 0, w | row, w & ~row)
 
+    def taps(a):
+        return any(int(a[5 + 3 * k]) in TAPPED and int(a[5 + 3 * k]) != SRC["H_E"] for k in range(int(a[4])))   # (H_E is a state row: scn_needs_y)
+
+    ahead = [not any(taps(a) for a in AC[int(PH[p][0]):int(PH[p][0]) + int(PH[p][1])]) for p in range(n_ph)]
+    changed0 = st["env_changed"].copy() if "env_changed" in st else np.zeros(n, bool)
+    for p in range(n_ph):   # stage A of the device's walk: `always` actions that read no tapped output
+        m = (phase0 == p) & st["active"]
+        if ahead[p] and m.any():
+            for a in AC[int(PH[p][0]):int(PH[p][0]) + int(PH[p][1])]:
+                run(a, m)
+    if "retap" in st and "env_changed" in st and (st["env_changed"] & ~changed0).any():
+        st["retap"](st)
     for p in range(n_ph):
         m = (phase0 == p) & st["active"]
         if not m.any():
             continue
         a0, na, r0, nr = (int(v) for v in PH[p])
-        for a in AC[a0:a0 + na]:
-            run(a, m)
+        if not ahead[p]:
+            for a in AC[a0:a0 + na]:
+                run(a, m)
         left = m.copy()
         for r in RU[r0:r0 + nr]:
             if not left.any():
@@ -313,3 +388,72 @@ def evaluate_on_host(blob: np.ndarray, st: dict, t: float, dt: float) -> None:
             st["phase"][hold] = int(r[7])
             st["since"][hold] = st["step"]
             left &= ~hold
+
+
+def table_kinds(blob: np.ndarray):
+    """(source kinds, destination kinds) a packed table names"""
+    n_ph, n_rule, n_act = int(blob[1]), int(blob[2]), int(blob[3])
+    RU = blob[HDR + PH_REC * n_ph:HDR + PH_REC * n_ph + RULE_REC * n_rule].reshape(n_rule, RULE_REC)
+    AC = blob[HDR + PH_REC * n_ph + RULE_REC * n_rule:].reshape(n_act, ACT_REC)
+    srcs = {int(r[0]) for r in RU if int(r[2]) != CMP["always"]}
+    for a in AC:
+        srcs |= {int(a[5 + 3 * k]) for k in range(int(a[4]))}
+    return srcs, {int(a[0]) for a in AC}
+
+
+def host_callback(blob: np.ndarray, st: dict, dt: float, every: int = 1):
+    """The table as the `user_callback` of a Simulation (the host-callback form of a run: every step crosses to the host). st: phase, since, par, rec
+    as evaluate_on_host wants them; its `step` is counted here, and the table is evaluated behind every `every`-th step. Per evaluation the model's
+    inputs (and a Cessna172Xv2's control-law rows) come down and go back; the outputs the table names are fetched after an f_ode! — the three blocks
+    of the tapped outputs, or the whole record only for a table that names y_ — and the environment rows only for a table that names them, pushed
+    back through set_env only when a wind row has changed. Where an `always` action has written the wind ahead of a tapped read, the taps are fetched
+    again under the new rows (evaluate_on_host's `retap`), as the device's evaluation of f_ode! stands behind that write. Only the environment is
+    pushed for that second f_ode!: on the device stage (B) also sees the u / ui / cu an `always` action has just written, but none of the eight taps
+    (attitude, track, climb rate, EAS, weight on wheels) depends on them, so the bits agree; a tap that did would need those rows pushed here too."""
+    from .modeling import f_ode
+    srcs, dsts = table_kinds(blob)
+    if SRC["X"] in srcs:
+        raise ValueError("host_callback: x_ sources read the device's row order, which the host arrays do not have; evaluate such a table on the device")
+    ctl = bool(srcs & {SRC["CS"], SRC["CU"]}) or DST["CU"] in dsts
+    uses_env = SRC["ENV"] in srcs or DST["ENV"] in dsts
+    kin, air, ldg = K["FB_Y_KIN"], K["FB_Y_AIR"], K["FB_Y_LDG"]
+    st.setdefault("step", 0)
+
+    def callback(mdl):
+        st["step"] += 1
+        if st["step"] % every:
+            return
+        u, ui = mdl.u, mdl.ui
+        st.update(u=u, ui=ui, s=mdl.s, active=mdl.status == 0)
+        if ctl:
+            cu = mdl.cu
+            st.update(cu=cu, cs=mdl.cs)
+        if uses_env:
+            st["env"] = mdl.env
+            st["env_changed"] = np.zeros(mdl.n, bool)
+        def fetch(whole):
+            f_ode(mdl)
+            if whole:
+                y = st["y"] = mdl.y
+                k_, a_, l_ = y[kin:], y[air:], y[ldg:]
+            else:
+                y = mdl.y_fields("KIN", "AIR", "LDG")
+                k_, a_, l_ = y, y[air - kin:], y[air - kin + K["FB_Y_AERO"] - air:]
+            st.update(h_e=k_[20], psi=k_[0], theta=k_[1], phi=k_[2], chi=k_[38], EAS=a_[20], clm=-k_[36],
+                      on_gnd=((l_[1] + l_[12] + l_[23]) > 0).astype(np.float64))
+
+        def retap(_):   # the taps under the wind an `always` action has just written (the record y stays the one from before)
+            mdl.env = st["env"]
+            fetch(False)
+        if SRC["Y"] in srcs or srcs & set(TAPPED):
+            fetch(SRC["Y"] in srcs)
+            if srcs & set(TAPPED):
+                st["retap"] = retap
+        evaluate_on_host(blob, st, st["step"] * dt, dt)
+        if ctl:
+            mdl.cu = cu
+        mdl.u = u
+        mdl.ui = ui
+        if uses_env and st["env_changed"].any():
+            mdl.env = st["env"]
+    return callback

@@ -289,6 +289,11 @@ Base.getproperty(sim::BatchedSimulation, s::Symbol) = s === :t ? getfield(sim, :
 # destination; a Cessna172Sv0 world (fp64, any mechanisation) takes tables that write the vehicle's inputs and records — the nlsim_q / nlsim_θ
 # elevator step, c172_demos.jl:108-206 — and the library refuses control-law rows (sources CS / CU, destination CU) on it, with the reason.
 const TABLE_SCENARIO = Cint(6)
+# the world's kinds of a blob (FB_SCN_SRC_ENV, FB_SCN_SRC_Y, FB_SCN_DST_ENV): the aircraft's own environment rows — a world whose rows are set
+# (fb_set_env) only; a table writes the three wind rows — and any row of mdl.y at the state behind the step
+const SCN_SRC_ENV = Cint(18)
+const SCN_SRC_Y = Cint(19)
+const SCN_DST_ENV = Cint(4)
 function set_scenario!(w::BatchedWorld, blob::Vector{Float64}, par::Union{Matrix{Float64}, Nothing} = nothing; every::Integer = 1)
     len = Ref{Int64}(length(blob))
     check(ccall((:fb_set_table, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Int64}, Cint), w.handle, TABLE_SCENARIO, blob, len, 1))

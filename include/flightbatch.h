@@ -429,12 +429,30 @@ int32_t fb_set_status(fb_handle h, const int32_t* status);
  * loaded. A Cessna172Xv2 handle takes every source and destination, FB_SCN_SRC_X rows < FB_X2_NX. A Cessna172Sv0 handle created with FB_F64
  * (any mechanisation, with or without fb_set_env rows) has no control-law rows: FB_SCN_SRC_CS, FB_SCN_SRC_CU and FB_SCN_DST_CU are refused,
  * FB_SCN_SRC_X rows < FB_NX; its scripts write the vehicle's inputs (FB_SCN_DST_U, _UI: `act.u.elevator += 0.1`, c172_demos.jl:108-206) and
- * records. FB_F32 handles and Robot2D refuse the table. */
+ * records. FB_F32 handles and Robot2D refuse the table.
+ * The world as well as the aircraft (the reference's scripts set `world.atmosphere.wind.u.N / .E`, c172_demos.jl:225-228, 427-433, and may read
+ * anything in mdl.y, FC/sim.jl:185, 279, 334-336), on a handle whose per-aircraft environment rows are set (fb_set_env):
+ *   FB_SCN_SRC_ENV  row = FB_ENV_* (all six): the aircraft's own environment row, as fb_get_env returns it.
+ *   FB_SCN_DST_ENV  row = FB_ENV_WIND_N / _E / _D only: the aircraft's wind. Written only when the value differs, and then like a changed input (the
+ *                   derivative a Cessna172Xv2 handle carries between launches is dropped for that aircraft). FB_ENV_T_SL / FB_ENV_P_SL are refused: each
+ *                   carries two derived rows that fb_set_env fills with the host's log / exp / sqrt, which a device write could not reproduce bit for
+ *                   bit. FB_ENV_H_TERRAIN is refused: a constructor argument of HorizontalTerrain (FP/terrain.jl:34-38), not an input.
+ *   FB_SCN_SRC_Y    row in [0, Ny) of fb_dims: that row of mdl.y at the state behind the step (what fb_f_ode + fb_get_outputs give at that instant),
+ *                   read before any action of the evaluation runs. A table that names it makes fb_step refresh the whole output record ahead of
+ *                   every evaluation (one f_ode! pass, counted by fb_timing_end among the launches); a table that does not pays nothing.
+ *                   The record is the one BEFORE the evaluation's actions: after an `always` action has written the wind, FB_SCN_SRC_EAS (tapped from
+ *                   the evaluation of f_ode! the walk itself makes, behind that write) and the record's EAS row differ within one evaluation.
+ *                   The refresh is an fb_f_ode like any other: an aircraft whose state behind the step makes f_ode! throw gets its status bit and the
+ *                   record (FB_TERM_OUTSIDE_STEP, the step count) THERE, and this very evaluation skips it. Without the kind the table would still
+ *                   evaluate that aircraft, and the next stepping launch would terminate it with its own FB_TERM_* code. (The device log's save has
+ *                   the same effect; here it changes what a table does.)
+ * A table with either ENV kind is refused on a handle without rows (call fb_set_env first), and while it is loaded fb_set_env(h, NULL) is refused
+ * (fb_scenario_configure(h, 0) first). */
 enum { FB_SCN_HDR = 8, FB_SCN_PHASE_REC = 4, FB_SCN_RULE_REC = 8, FB_SCN_ACT_REC = 14, FB_SCN_NTERM = 3 };
 enum { FB_SCN_SRC_CONST = 0, FB_SCN_SRC_T, FB_SCN_SRC_T_IN_PHASE, FB_SCN_SRC_X, FB_SCN_SRC_CS, FB_SCN_SRC_CU, FB_SCN_SRC_U, FB_SCN_SRC_S,
        FB_SCN_SRC_ON_GND, FB_SCN_SRC_H_E, FB_SCN_SRC_PSI, FB_SCN_SRC_THETA, FB_SCN_SRC_PHI, FB_SCN_SRC_CHI, FB_SCN_SRC_EAS, FB_SCN_SRC_CLM,
-       FB_SCN_SRC_PAR, FB_SCN_SRC_REC, FB_SCN_NSRC };
-enum { FB_SCN_DST_CU = 0, FB_SCN_DST_U, FB_SCN_DST_UI, FB_SCN_DST_REC, FB_SCN_NDST };
+       FB_SCN_SRC_PAR, FB_SCN_SRC_REC, FB_SCN_SRC_ENV, FB_SCN_SRC_Y, FB_SCN_NSRC };
+enum { FB_SCN_DST_CU = 0, FB_SCN_DST_U, FB_SCN_DST_UI, FB_SCN_DST_REC, FB_SCN_DST_ENV, FB_SCN_NDST };
 enum { FB_SCN_LT = 0, FB_SCN_GT, FB_SCN_GE, FB_SCN_LE, FB_SCN_EQ, FB_SCN_NE, FB_SCN_ALWAYS };
 /* fb_set_table(FB_TABLE_SCENARIO) validates every index of the blob, allocates the per-aircraft rows (phase 0, entry step 0, parameters and
  * records zero) and switches the evaluation on with every = 1. fb_scenario_configure: the period in steps (>= 1), or 0: scenario off, rows freed.
@@ -446,10 +464,12 @@ int32_t fb_scenario_get_state(fb_handle h, int32_t* phase /* [N] or NULL */, int
 int32_t fb_scenario_set_state(fb_handle h, const int32_t* phase, const int64_t* since_step, const double* rec /* each [..N] or NULL: left as is */);
 
 /* HIP-event timing on the handle's stream around the fb_step launches issued between begin and end;
- * reports total elapsed ms and the number of stepping-kernel launches. */
+ * reports total elapsed ms and the number of stepping-kernel launches (plus the output-record refreshes of a FB_SCN_SRC_Y table). */
 int32_t fb_timing_begin(fb_handle h);
 int32_t fb_timing_end(fb_handle h, float* ms, int64_t* n_launches);
-/* The same window with ONE event pair per stepping launch (both passes of a launch between its pair), up to max_launches of them;
+/* (Under a table that names FB_SCN_SRC_Y, n_launches of fb_timing_end includes the output-record refreshes, one per evaluation; the per-launch
+ * stamps below cover stepping launches only, so *n of fb_timing_launches is smaller than n_launches then, and ms / n_launches is not a time per stepping launch.)
+ * The same window with ONE event pair per stepping launch (both passes of a launch between its pair), up to max_launches of them;
  * after fb_timing_end, fb_timing_launches returns their durations in launch order (ms[0 .. min(*n, cap))), *n = pairs recorded.
  * A measurement aid (bench.py reports median / min / max over launches and warms up until launches agree); no reference counterpart. */
 int32_t fb_timing_begin_per_launch(fb_handle h, int64_t max_launches);
