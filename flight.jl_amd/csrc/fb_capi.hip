@@ -13,6 +13,7 @@
 #include "robot2d_kernels.hpp"
 #include "scenario_kernels.hpp"
 #include "lin_kernels.hpp"
+#include "lss_kernels.hpp"
 
 using namespace fbd;
 
@@ -91,6 +92,8 @@ struct fb_handle_s {
     bool scn_env = false, scn_y = false;   // the loaded table names FB_SCN_SRC_ENV / FB_SCN_DST_ENV (the rows must stay); FB_SCN_SRC_Y (fb_step refreshes y ahead of an evaluation)
     // fb_linearize / fb_linearize_state: device rows of the results (ẋ0 x0 u0 y0 | A B | C D) and the status OR, kept and grown on demand
     double* lin_buf = nullptr; size_t lin_doubles = 0; int32_t* lin_st = nullptr;
+    uint32_t lin_have = 0; int lin_nx = 0, lin_nu = 0, lin_ny = 0;   // which blocks of lin_buf the last run wrote (LIN_HAVE_*, fb_lss.inc) and their dimensions
+    struct LssState* lss = nullptr;  // LinearizedSS handles only (fb_lss.inc)
 };
 
 static KArgs make_args(fb_handle h) {
@@ -208,6 +211,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 
 #include "fb_robot2d.inc"
 #include "fb_log.inc"
+#include "fb_lss.inc"
 struct ncclUniqueIdBlob { char internal[128]; };   // ncclUniqueId (rccl.h:40-43), passed by value
 
 // The scratch rows of the stepping kernels (ctl_bak, duo_pld, duo_tap) are zeroed when a handle is created: hipMalloc hands out zero pages in
@@ -462,6 +466,7 @@ const char* fb_version(void) { return "flightbatch 0.1 (gfx950)"; }
 int32_t fb_create(int32_t model_id, int32_t kin_id, int32_t dtype, int64_t n, int32_t device_id, fb_handle* out) {
     if (!out) return fail("out is null");
     *out = nullptr;
+    if (model_id == FB_MODEL_LSS) return fail("fb_create: a LinearizedSS handle (FB_MODEL_LSS) needs its dimensions: create it with fb_lss_create or fb_lss_from_linearization");
     if (model_id != FB_MODEL_C172S0 && model_id != FB_MODEL_C172X2 && model_id != FB_MODEL_ROBOT2D) return fail("unknown model id");
     if ((model_id == FB_MODEL_C172S0 || model_id == FB_MODEL_C172X2) && kin_id != FB_KIN_WA && kin_id != FB_KIN_ECEF && kin_id != FB_KIN_NED) return fail("unknown kinematics id");
     if (model_id == FB_MODEL_C172X2 && dtype != FB_F64) return fail("Cessna172Xv2: only FB_F64 is implemented");
@@ -497,6 +502,7 @@ int32_t fb_destroy(fb_handle h) {
     log_free(h);
     scn_free(h);
     r2_destroy(h);
+    lss_destroy(h);
     hipFree(h->x_own); hipFree(h->s_own); hipFree(h->u); hipFree(h->ui); hipFree(h->status); hipFree(h->term_step); hipFree(h->term_where); hipFree(h->y); hipFree(h->xdot);
     hipFree(h->tables); hipFree(h->tables_f32); hipFree(h->egm96); hipFree(h->trim_buf); hipFree(h->trim_ok); hipFree(h->trim_ws); hipFree(h->env_rows);
     hipFree(h->cs); hipFree(h->cu); hipFree(h->q_pre); hipFree(h->ctl_bak); hipFree(h->duo_pld); hipFree(h->duo_tap); hipFree(h->gains); hipFree(h->redo); hipFree(h->k1); hipFree(h->k1_valid);
@@ -510,6 +516,13 @@ int32_t fb_destroy(fb_handle h) {
 int64_t fb_size(fb_handle h) { return h ? h->n : -1; }
 int32_t fb_dims(fb_handle h, int32_t* nx, int32_t* ns, int32_t* nu, int32_t* ny) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) {
+        if (nx) *nx = h->lss->nx;
+        if (ns) *ns = 0;
+        if (nu) *nu = h->lss->nu;
+        if (ny) *ny = h->lss->ny;
+        return 0;
+    }
     const bool r2 = h->model == FB_MODEL_ROBOT2D;
     if (nx) *nx = r2 ? (int)FB_R2_NX : nx_of(h);
     if (ns) *ns = r2 ? 0 : FB_NS;
@@ -529,6 +542,7 @@ int32_t fb_attach_state(fb_handle h, void* x_dev, void* s_dev) {
     if (h) fsal_invalidate(h);
     if (!h) return fail("null handle");
     if (h->model == FB_MODEL_ROBOT2D) return fail("fb_attach_state: not supported for Robot2D");
+    if (is_lss(h)) return lss_refuse("fb_attach_state", "its state rows are the handle's own");
     if ((x_dev == nullptr) != (s_dev == nullptr)) return fail("x_dev and s_dev must both be given or both be NULL");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -550,6 +564,7 @@ static int32_t put_coarse_knots(fb_handle h, int slot, const double* k, int n) {
 int32_t fb_set_table(fb_handle h, int32_t kind, const void* data, const int64_t* dims, int32_t ndims) {
     if (h) fsal_invalidate(h);
     if (!h || !data || !dims) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_set_table", "a linear model reads no tables (its matrices: fb_lss_set_model)");
     HIPCHK(hipSetDevice(h->device));
     // fb_step is asynchronous on the handle's non-blocking stream: the uploads below (null-stream copies, a re-allocated gains
     // blob) must not overtake stepping kernels that are still queued or running with the old tables
@@ -648,6 +663,7 @@ int32_t fb_get_params(fb_handle h, fb_params* p) {
 int32_t fb_set_env(fb_handle h, const double* env) {
     if (!h) return fail("null handle");
     if (h->model == FB_MODEL_ROBOT2D) return fail("Robot2D has no environment");
+    if (is_lss(h)) return lss_refuse("fb_set_env", "a linear model has no environment");
     fsal_invalidate(h);
     HIPCHK(hipSetDevice(h->device));
     if (!env) {
@@ -689,6 +705,7 @@ int32_t fb_has_env(fb_handle h) {
 }
 int32_t fb_get_env(fb_handle h, double* env) {
     if (!h || !env) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_get_env", "a linear model has no environment");
     if (!h->env_rows) return fail("no per-aircraft environment rows are set (fb_set_env): the batch-wide block is fb_get_params'");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -707,6 +724,11 @@ static int32_t set_state_impl(fb_handle h, const double* x, const int32_t* s, bo
         if (init) { h->r2->steps_done = 0; h->t = 0.0; }
         return 0;
     }
+    if (is_lss(h)) {   // (no discrete states: s is not read)
+        if (x) { if (int32_t rc = lss_rows(h, h->x, x, nullptr, h->lss->nx)) return rc; }
+        if (init) { HIPCHK(clear_terminations(h)); HIPCHK(hipStreamSynchronize(h->stream)); h->t = 0.0; h->steps_done = 0; }
+        return 0;
+    }
     if (x) { if (int32_t rc = copy_rows(h, h->x, x, nullptr, nx_of(h), row_map_of(h))) return rc; }
     if (s) HIPCHK(hipMemcpyAsync(h->s, s, sizeof(int32_t) * FB_NS * h->n, hipMemcpyHostToDevice, h->stream));
     if (init) HIPCHK(clear_terminations(h));  // init! clears terminations (sim.jl:390-414)
@@ -720,6 +742,7 @@ int32_t fb_get_state(fb_handle h, double* x, int32_t* s) {
     if (!h) return fail("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (h->model == FB_MODEL_ROBOT2D) return x ? r2_download(h, h->r2, x, h->r2->r, FB_R2_NX) : 0;
+    if (is_lss(h)) return x ? lss_rows(h, h->x, nullptr, x, h->lss->nx) : 0;
     if (x) { if (int32_t rc = copy_rows(h, h->x, nullptr, x, nx_of(h), row_map_of(h))) return rc; }
     if (s) HIPCHK(hipMemcpyAsync(s, h->s, sizeof(int32_t) * FB_NS * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -730,6 +753,7 @@ int32_t fb_set_inputs(fb_handle h, const double* u, const int32_t* ui) {
     if (!h) return fail("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (h->model == FB_MODEL_ROBOT2D) return u ? r2_upload(h, h->r2, h->r2->u, u, FB_R2_NU) : 0;
+    if (is_lss(h)) return u ? lss_rows(h, h->u, u, nullptr, h->lss->nu) : 0;   // (no integer inputs: ui is not read)
     if (u) HIPCHK(hipMemcpyAsync(h->u, u, sizeof(double) * FB_NU * h->n, hipMemcpyHostToDevice, h->stream));
     if (ui) HIPCHK(hipMemcpyAsync(h->ui, ui, sizeof(int32_t) * h->n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -739,6 +763,10 @@ int32_t fb_get_inputs(fb_handle h, double* u, int32_t* ui) {
     if (!h) return fail("null handle");
     HIPCHK(hipSetDevice(h->device));
     if (h->model == FB_MODEL_ROBOT2D) return u ? r2_download(h, h->r2, u, h->r2->u, FB_R2_NU) : 0;
+    if (is_lss(h)) {
+        if (ui) return lss_refuse("fb_get_inputs", "it has no integer inputs (pass ui = NULL)");
+        return u ? lss_rows(h, h->u, nullptr, u, h->lss->nu) : 0;
+    }
     if (u) HIPCHK(hipMemcpyAsync(u, h->u, sizeof(double) * FB_NU * h->n, hipMemcpyDeviceToHost, h->stream));
     if (ui) HIPCHK(hipMemcpyAsync(ui, h->ui, sizeof(int32_t) * h->n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -747,6 +775,7 @@ int32_t fb_get_inputs(fb_handle h, double* u, int32_t* ui) {
 
 int32_t fb_f_init(fb_handle h, const double* init, int32_t ninit) {
     if (!h || (!init && ninit != 0)) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_f_init", "it starts at X = copy(x0), U = copy(u0) (fb_lss_set_model) or at the state fb_set_state gives it");
     HIPCHK(hipSetDevice(h->device));
     if (h->model == FB_MODEL_ROBOT2D) return r2_f_init(h, init, ninit);
     if (is_x2(h) && ninit == 0) {   // f_init!(avionics, vehicle) on the state the host has set
@@ -763,6 +792,7 @@ int32_t fb_f_init(fb_handle h, const double* init, int32_t ninit) {
 int32_t fb_trim(fb_handle h, const double* trim_params, double* trim_state, int32_t* success, double* cost) {
     if (h) fsal_invalidate(h);
     if (h && h->model == FB_MODEL_ROBOT2D) return fail("fb_trim: Robot2D has no trim (use fb_f_init)");
+    if (h && is_lss(h)) return lss_refuse("fb_trim", "a linear model has no trim (it is the result of one)");
     if (int32_t rc = check_ready_x2(h)) return rc;
     if (!trim_params || !trim_state) return fail("null argument");
     HIPCHK(hipSetDevice(h->device));
@@ -771,6 +801,7 @@ int32_t fb_trim(fb_handle h, const double* trim_params, double* trim_state, int3
 
 int32_t fb_f_ode(fb_handle h, double* xdot) {
     if (h && h->model == FB_MODEL_ROBOT2D) { HIPCHK(hipSetDevice(h->device)); return r2_f_ode(h, xdot); }
+    if (h && is_lss(h)) { HIPCHK(hipSetDevice(h->device)); return lss_f_ode(h, xdot); }
     if (int32_t rc = check_ready(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
     const int64_t n = h->n;
@@ -787,6 +818,7 @@ int32_t fb_f_ode(fb_handle h, double* xdot) {
     return 0;
 }
 int32_t fb_f_step(fb_handle h) {
+    if (h && is_lss(h)) return 0;   // @no_step LinearizedSS (FP/linearization.jl:162)
     if (h) fsal_invalidate(h);
     if (h && h->model == FB_MODEL_ROBOT2D) {
         if (int32_t rc = r2_ready(h)) return rc;
@@ -803,6 +835,7 @@ int32_t fb_f_step(fb_handle h) {
 }
 int32_t fb_f_periodic(fb_handle h) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return 0;   // @no_periodic LinearizedSS (FP/linearization.jl:161)
     if (h->model == FB_MODEL_ROBOT2D) {
         if (int32_t rc = r2_ready(h)) return rc;
         HIPCHK(hipSetDevice(h->device));
@@ -822,6 +855,7 @@ int32_t fb_f_periodic(fb_handle h) {
 /* avionics.ctl.u / avionics.ctl.{s,y} of Cessna172Xv2 */
 int32_t fb_set_ctl_inputs(fb_handle h, const double* cu) {
     if (!h || !cu) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_set_ctl_inputs", "only Cessna172Xv2 has control laws");
     if (!is_x2(h)) return fail("fb_set_ctl_inputs: only Cessna172Xv2 has control laws");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->cu, cu, sizeof(double) * FB_NCU * h->n, hipMemcpyHostToDevice, h->stream));
@@ -830,6 +864,7 @@ int32_t fb_set_ctl_inputs(fb_handle h, const double* cu) {
 }
 int32_t fb_get_ctl_inputs(fb_handle h, double* cu) {
     if (!h || !cu) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_get_ctl_inputs", "only Cessna172Xv2 has control laws");
     if (!is_x2(h)) return fail("fb_get_ctl_inputs: only Cessna172Xv2 has control laws");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(cu, h->cu, sizeof(double) * FB_NCU * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -838,6 +873,7 @@ int32_t fb_get_ctl_inputs(fb_handle h, double* cu) {
 }
 int32_t fb_set_ctl_state(fb_handle h, const double* cs) {
     if (!h || !cs) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_set_ctl_state", "only Cessna172Xv2 has control laws");
     if (!is_x2(h)) return fail("fb_set_ctl_state: only Cessna172Xv2 has control laws");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->cs, cs, sizeof(double) * FB_NCS * h->n, hipMemcpyHostToDevice, h->stream));
@@ -846,6 +882,7 @@ int32_t fb_set_ctl_state(fb_handle h, const double* cs) {
 }
 int32_t fb_get_ctl_state(fb_handle h, double* cs) {
     if (!h || !cs) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_get_ctl_state", "only Cessna172Xv2 has control laws");
     if (!is_x2(h)) return fail("fb_get_ctl_state: only Cessna172Xv2 has control laws");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(cs, h->cs, sizeof(double) * FB_NCS * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -855,6 +892,7 @@ int32_t fb_get_ctl_state(fb_handle h, double* cs) {
 int32_t fb_get_outputs(fb_handle h, double* y) {
     if (!h || !y) return fail("null argument");
     if (h->model == FB_MODEL_ROBOT2D) { HIPCHK(hipSetDevice(h->device)); return r2_download(h, h->r2, y, h->r2->y, FB_R2_NY); }
+    if (is_lss(h)) { HIPCHK(hipSetDevice(h->device)); return lss_rows(h, h->y, nullptr, y, h->lss->ny); }
     if (!h->y) return fail("no outputs yet: call fb_f_ode first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(y, h->y, sizeof(double) * FB_NY * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -864,6 +902,7 @@ int32_t fb_get_outputs(fb_handle h, double* y) {
 int32_t fb_get_output_fields(fb_handle h, uint32_t field_mask, double* y) {
     if (!h || !y) return fail("null argument");
     if (h->model == FB_MODEL_ROBOT2D) return fail("fb_get_output_fields: Robot2D's output record has no blocks (use fb_get_outputs)");
+    if (is_lss(h)) return lss_refuse("fb_get_output_fields", "its output record has no blocks (use fb_get_outputs)");
     if (!h->y) return fail("no outputs yet: call fb_f_ode first");
     if (field_mask == 0 || (field_mask & ~(uint32_t)FB_YF_ALL)) return fail("fb_get_output_fields: unknown bits in field_mask 0x%x", field_mask);
     static const int first[8] = {FB_Y_KIN, FB_Y_AIR, FB_Y_AERO, FB_Y_LDG, FB_Y_PWP, FB_Y_FUEL, FB_Y_DYN, FB_NY};
@@ -914,6 +953,7 @@ static void launch_step(fb_handle h, dim3 grid, const KArgs& a, int k) {
 // nsteps of the stepping kernel, no logging
 static int32_t step_raw(fb_handle h, int64_t nsteps) {
     if (h->model == FB_MODEL_ROBOT2D) return r2_step(h, nsteps);
+    if (is_lss(h)) return lss_step(h, nsteps);
     if (h->dtype == FB_F32 && h->tables_f32_stale) {   // fp32 mirror of the table blob for the fp32 stepper
         HIPCHK(hipStreamSynchronize(h->stream));       // kernels already queued still read the old mirror
         std::vector<double> d(TABLE_BUF_DOUBLES);
@@ -946,6 +986,8 @@ static int32_t step_raw(fb_handle h, int64_t nsteps) {
 int32_t fb_step(fb_handle h, int64_t nsteps) {
     if (h && h->model == FB_MODEL_ROBOT2D) {
         if (int32_t rc = r2_ready(h)) return rc;
+    } else if (h && is_lss(h)) {
+        if (int32_t rc = lss_ready(h)) return rc;
     } else if (int32_t rc = check_ready_x2(h)) return rc;
     if (nsteps < 0) return fail("nsteps must be >= 0");
     HIPCHK(hipSetDevice(h->device));
@@ -979,10 +1021,10 @@ int32_t fb_log_configure(fb_handle h, int64_t every, int64_t capacity, const int
     log_free(h);
     if (every <= 0) return 0;  // logging off
     if (capacity <= 0 || nrows <= 0 || !rows) return fail("fb_log_configure: capacity and the row list must be non-empty");
-    const int ny = h->model == FB_MODEL_ROBOT2D ? FB_R2_NY : FB_NY, nx = h->model == FB_MODEL_ROBOT2D ? (int)FB_R2_NX : nx_of(h);
+    const int ny = is_lss(h) ? h->lss->ny : h->model == FB_MODEL_ROBOT2D ? FB_R2_NY : FB_NY, nx = is_lss(h) ? h->lss->nx : h->model == FB_MODEL_ROBOT2D ? (int)FB_R2_NX : nx_of(h);
     LogState* L = new LogState();
     std::vector<int32_t> dev_rows(rows, rows + nrows);   // state rows are given in the C ABI's order; the gather works on device rows
-    const row_map_t map = h->model == FB_MODEL_ROBOT2D ? nullptr : row_map_of(h);
+    const row_map_t map = (h->model == FB_MODEL_ROBOT2D || is_lss(h)) ? nullptr : row_map_of(h);
     for (int j = 0; j < nrows; j++) {
         const int r = rows[j];
         const bool ok = (r >= 0 && r < ny) || (r >= FB_LOG_X0 && r < FB_LOG_X0 + nx);
@@ -1058,6 +1100,7 @@ int32_t fb_set_step_count(fb_handle h, int64_t count, double t) {
 }
 int32_t fb_set_status(fb_handle h, const int32_t* status) {
     if (!h || !status) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_set_status", "a linear model throws nothing, its status words stay 0 (checkpoints are not implemented for it)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->status, status, sizeof(int32_t) * h->n, hipMemcpyHostToDevice, h->stream));
     const long long step0 = h->model == FB_MODEL_ROBOT2D ? (long long)h->r2->steps_done : (long long)h->steps_done;
@@ -1068,6 +1111,7 @@ int32_t fb_set_status(fb_handle h, const int32_t* status) {
 }
 int32_t fb_set_termination(fb_handle h, const int64_t* step, const int32_t* where) {
     if (!h || !step || !where) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_set_termination", "a linear model throws nothing (checkpoints are not implemented for it)");
     HIPCHK(hipSetDevice(h->device));
     std::vector<int32_t> st((size_t)h->n), wh((size_t)h->n);
     std::vector<long long> ts((size_t)h->n);
@@ -1118,6 +1162,7 @@ int32_t fb_status(fb_handle h, int32_t* status) {
 }
 int32_t fb_get_termination(fb_handle h, int64_t* step, int32_t* where) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return lss_refuse("fb_get_termination", "a linear model throws nothing: it never terminates");
     HIPCHK(hipSetDevice(h->device));
     std::vector<int32_t> st((size_t)h->n);
     std::vector<long long> ts(step ? (size_t)h->n : 0);
@@ -1137,6 +1182,7 @@ int32_t fb_get_termination(fb_handle h, int64_t* step, int32_t* where) {
 
 int32_t fb_scenario_configure(fb_handle h, int32_t every) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return lss_refuse("fb_scenario_configure", "scenario tables drive the inputs of a Cessna172Sv0 or a Cessna172Xv2");
     if (every < 0) return fail("fb_scenario_configure: the evaluation period must be >= 1 step (0: scenario off)");
     HIPCHK(hipSetDevice(h->device));
     if (every == 0) { HIPCHK(hipStreamSynchronize(h->stream)); scn_free(h); return 0; }
@@ -1146,6 +1192,7 @@ int32_t fb_scenario_configure(fb_handle h, int32_t every) {
 }
 int32_t fb_scenario_set_params(fb_handle h, const double* par) {
     if (!h || !par) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_scenario_*", "scenario tables drive the inputs of a Cessna172Sv0 or a Cessna172Xv2");
     if (!h->scn_prog) return fail("no scenario table is loaded (fb_set_table FB_TABLE_SCENARIO)");
     HIPCHK(hipSetDevice(h->device));
     if (h->scn_npar > 0) HIPCHK(hipMemcpyAsync(h->scn_par, par, sizeof(double) * h->scn_npar * h->n, hipMemcpyHostToDevice, h->stream));
@@ -1154,6 +1201,7 @@ int32_t fb_scenario_set_params(fb_handle h, const double* par) {
 }
 int32_t fb_scenario_get_params(fb_handle h, double* par) {
     if (!h || !par) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_scenario_*", "scenario tables drive the inputs of a Cessna172Sv0 or a Cessna172Xv2");
     if (!h->scn_prog) return fail("no scenario table is loaded (fb_set_table FB_TABLE_SCENARIO)");
     HIPCHK(hipSetDevice(h->device));
     if (h->scn_npar > 0) HIPCHK(hipMemcpyAsync(par, h->scn_par, sizeof(double) * h->scn_npar * h->n, hipMemcpyDeviceToHost, h->stream));
@@ -1162,6 +1210,7 @@ int32_t fb_scenario_get_params(fb_handle h, double* par) {
 }
 int32_t fb_scenario_get_state(fb_handle h, int32_t* phase, int64_t* since_step, double* rec) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return lss_refuse("fb_scenario_*", "scenario tables drive the inputs of a Cessna172Sv0 or a Cessna172Xv2");
     if (!h->scn_prog) return fail("no scenario table is loaded (fb_set_table FB_TABLE_SCENARIO)");
     HIPCHK(hipSetDevice(h->device));
     static_assert(sizeof(long long) == sizeof(int64_t), "");
@@ -1173,6 +1222,7 @@ int32_t fb_scenario_get_state(fb_handle h, int32_t* phase, int64_t* since_step, 
 }
 int32_t fb_scenario_set_state(fb_handle h, const int32_t* phase, const int64_t* since_step, const double* rec) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return lss_refuse("fb_scenario_*", "scenario tables drive the inputs of a Cessna172Sv0 or a Cessna172Xv2");
     if (!h->scn_prog) return fail("no scenario table is loaded (fb_set_table FB_TABLE_SCENARIO)");
     if (phase)
         for (int64_t i = 0; i < h->n; i++)

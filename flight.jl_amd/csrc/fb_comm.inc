@@ -56,6 +56,7 @@ int32_t fb_comm_unique_id(char* id128) {
 int32_t fb_comm_destroy(void* comm);
 int32_t fb_comm_init(fb_handle h, int32_t world, int32_t rank, const char* id128, void** comm) {
     if (!h || !id128 || !comm) return fail("null argument");
+    if (is_lss(h)) return lss_refuse("fb_comm_init", "gathering LinearizedSS states over RCCL is not implemented");
     if (world < 1 || rank < 0 || rank >= world) return fail("fb_comm_init: rank %d of %d", rank, world);
     if (int32_t rc = rccl_load()) return rc;
     HIPCHK(hipSetDevice(h->device));   // one communicator per rank, on the handle's GPU
@@ -99,6 +100,7 @@ int32_t fb_comm_shard_sizes(void* comm, int64_t* n_of, int64_t* n_max) {
 int32_t fb_gather_state(fb_handle h, void* comm, double* recv_dev) {
     if (!h || !comm || !recv_dev) return fail("null argument");
     if (h->model == FB_MODEL_ROBOT2D) return fail("fb_gather_state: not available for Robot2D handles");
+    if (is_lss(h)) return lss_refuse("fb_gather_state", "gathering LinearizedSS states over RCCL is not implemented");
     if (int32_t rc = rccl_load()) return rc;
     FbComm* c = (FbComm*)comm;
     if (c->n_of[c->rank] != h->n) return fail("fb_gather_state: the communicator was initialised with a handle of %lld aircraft, this one holds %lld", (long long)c->n_of[c->rank], (long long)h->n);

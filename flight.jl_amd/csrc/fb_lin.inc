@@ -4,6 +4,7 @@
 // the reference has get_x_ss / get_u_ss / get_y_ss for Vehicle{NED} and Robot2D only (c172s.jl:397-400, c172x.jl:452-455, robot2d.jl:253-275)
 static int32_t lin_supported(fb_handle h) {
     if (!h) return fail("null handle");
+    if (is_lss(h)) return lss_refuse("linearize", "the handle IS a linearisation; the reference defines linearize for vehicles");
     if (h->dtype != FB_F64) return fail("linearize: FB_F32 handles are not supported (the Jacobians are fp64 differences)");
     if (h->model == FB_MODEL_ROBOT2D) return 0;
     if (h->kin != FB_KIN_NED) return fail("linearize: Cessna172Sv0 / Cessna172Xv2 have a state-space model with NED kinematics only (the reference defines get_x_ss for Vehicle{NED})");
@@ -48,6 +49,7 @@ static int32_t lin_run(fb_handle h, const KArgs& a, int32_t scheme, const LinHos
     double* tAB = CD + (int64_t)ny * nc * n;
     double* tCD = tAB + (int64_t)nx * nc * n;
     const bool want_ab = out.A || out.B, want_cd = out.C || out.D;
+    h->lin_have = 0;   // (set again below, once the launches are queued; what fb_lss_from_linearization may read)
     const dim3 gb = grid_for(n, 256), gd(gb.x, (unsigned)nc);
     if (h->model == FB_MODEL_ROBOT2D) {
         HIPCHK(hipMemsetAsync(h->lin_st, 0, sizeof(int32_t) * n, h->stream));   // (Robot2D's f_ode! throws nothing)
@@ -73,6 +75,8 @@ static int32_t lin_run(fb_handle h, const KArgs& a, int32_t scheme, const LinHos
         else launch(std::false_type{});
     }
     HIPCHK(hipGetLastError());
+    h->lin_have = LIN_HAVE_BASE | (out.x0 ? LIN_HAVE_X0 : 0) | (out.u0 ? LIN_HAVE_U0 : 0) | (want_ab ? LIN_HAVE_AB : 0) | (want_cd ? LIN_HAVE_CD : 0);
+    h->lin_nx = nx; h->lin_nu = nu; h->lin_ny = ny;
     auto get = [&](double* host, const double* dev, int64_t rows) -> int32_t {
         if (host) HIPCHK(hipMemcpyAsync(host, dev, sizeof(double) * rows * n, hipMemcpyDeviceToHost, h->stream));
         return 0;

@@ -241,6 +241,65 @@ f_ode!(w::BatchedWorld) = (check(ccall((:fb_f_ode, lib), Cint, (Ptr{Cvoid}, Ptr{
 f_step!(w::BatchedWorld) = (check(ccall((:fb_f_step, lib), Cint, (Ptr{Cvoid},), w.handle)); nothing)
 f_periodic!(w::BatchedWorld) = (check(ccall((:fb_f_periodic, lib), Cint, (Ptr{Cvoid},), w.handle)); nothing)
 
+# ---- Model(lss) on the device (FB_MODEL_LSS; FP/linearization.jl:157-192): N linear models of one (nx, nu, ny), each with its own matrices
+"N instances of `Model(lss::LinearizedSS)` resident on one GPU. Built from the named tuple `linearize(world, trim)` returns
+(`LinearWorld(lin)`), or device to device from the world that was linearised (`linear_world(world; ix, iu, iy)`, the reference's `subsystem`)."
+mutable struct LinearWorld <: ModelDefinition
+    handle::Ptr{Cvoid}
+    n::Int
+    nx::Int
+    nu::Int
+    ny::Int
+    function LinearWorld(handle::Ptr{Cvoid})
+        nx, nu, ny = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+        check(ccall((:fb_dims, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}, Ptr{Cint}), handle, nx, C_NULL, nu, ny))
+        w = new(handle, ccall((:fb_size, lib), Int64, (Ptr{Cvoid},), handle), nx[], nu[], ny[])
+        finalizer(w -> ccall((:fb_destroy, lib), Cint, (Ptr{Cvoid},), w.handle), w)
+        return w
+    end
+end
+function LinearWorld(lin; device::Integer = 0)
+    n, nx = size(lin.x0); nu = size(lin.u0, 2); ny = size(lin.y0, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_create, lib), Cint, (Cint, Cint, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}), nx, nu, ny, n, device, h))
+    w = LinearWorld(h[])
+    check(ccall((:fb_lss_set_model, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}), w.handle, lin.xdot0, lin.x0, lin.u0, lin.y0, lin.a, lin.b, lin.c, lin.d))
+    return w
+end
+"`Model(subsystem(lss; x, u, y))` from the result of the last `linearize(world, trim)`, which is still on the device: ix, iu, iy are 1-based
+index vectors into the state-space vectors (`nothing`: every index)."
+function linear_world(w::BatchedWorld; ix = nothing, iu = nothing, iy = nothing)
+    zero_based(v) = v === nothing ? Cint[] : Cint.(v .- 1)
+    jx, ju, jy = zero_based(ix), zero_based(iu), zero_based(iy)
+    arg(v, j) = v === nothing ? C_NULL : j      # (ccall converts and roots a Vector{Cint} itself)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_from_linearization, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint, Ptr{Cint}, Cint, Ptr{Cint}, Cint, Ptr{Ptr{Cvoid}}),
+                w.handle, arg(ix, jx), length(jx), arg(iu, ju), length(ju), arg(iy, jy), length(jy), h))
+    return LinearWorld(h[])
+end
+f_ode!(w::LinearWorld) = (check(ccall((:fb_f_ode, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, C_NULL)); nothing)
+f_step!(w::LinearWorld) = nothing        # @no_step LinearizedSS
+f_periodic!(w::LinearWorld) = nothing    # @no_periodic LinearizedSS
+state(w::LinearWorld) = (x = Matrix{Float64}(undef, w.n, w.nx);
+    check(ccall((:fb_get_state, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}), w.handle, x, C_NULL)); x)
+outputs(w::LinearWorld) = (y = Matrix{Float64}(undef, w.n, w.ny);
+    check(ccall((:fb_get_outputs, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, y)); y)
+inputs!(w::LinearWorld, u::Matrix{Float64}) = (size(u) == (w.n, w.nu) || throw(DimensionMismatch("u must be N x nu"));
+    check(ccall((:fb_set_inputs, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Int32}), w.handle, u, C_NULL)); nothing)
+"nsteps of RK4 at dt with u held, `steps_per_launch` steps fused per kernel launch"
+function step!(w::LinearWorld, nsteps::Integer; dt::Real = 0.02, steps_per_launch::Integer = 50)
+    p = Ref{Params}()
+    check(ccall((:fb_get_params, lib), Cint, (Ptr{Cvoid}, Ptr{Params}), w.handle, p))
+    q = p[]
+    p[] = Params(dt, q.periodic_n, q.surface, q.T_sl, q.p_sl, q.wind_ned, q.h_terrain)
+    check(ccall((:fb_set_params, lib), Cint, (Ptr{Cvoid}, Ptr{Params}), w.handle, p))
+    check(ccall((:fb_set_steps_per_launch, lib), Cint, (Ptr{Cvoid}, Cint), w.handle, steps_per_launch))
+    check(ccall((:fb_step, lib), Cint, (Ptr{Cvoid}, Int64), w.handle, nsteps))
+    check(ccall((:fb_sync, lib), Cint, (Ptr{Cvoid},), w.handle))
+    return nothing
+end
+
 "Simulation(world; dt, Δt) for the batch: fixed-step RK4 + Flight.jl's callback order, fused on the GPU."
 mutable struct BatchedSimulation
     mdl::BatchedWorld

@@ -29,7 +29,8 @@ extern "C" {
 typedef struct fb_handle_s* fb_handle;
 
 /* ---- model / kinematics / dtype ids -------------------------------------------------------- */
-enum { FB_MODEL_C172S0 = 0, FB_MODEL_C172X2 = 1, FB_MODEL_ROBOT2D = 2 }; /* FA/c172/c172s/c172s0.jl:14-18 */
+enum { FB_MODEL_C172S0 = 0, FB_MODEL_C172X2 = 1, FB_MODEL_ROBOT2D = 2, /* FA/c172/c172s/c172s0.jl:14-18 */
+       FB_MODEL_LSS = 3 };  /* Model(lss::LinearizedSS), FP/linearization.jl:157-192: created by fb_lss_create / fb_lss_from_linearization, not by fb_create */
 enum { FB_KIN_WA = 0, FB_KIN_ECEF = 1, FB_KIN_NED = 2 };                 /* FP/kinematics.jl:148,250,329   */
 /* The kinematic block of x follows the mechanisation (Modeling.X of each, kinematics.jl:152-153, 252-253, 331-332):
  * WA q_wb[4] q_ew[4] h_e (Nx = 27), ECEF q_eb[4] n_e[3] h_e (Nx = 26), NED psi theta phi lat lon h_e (Nx = 24); the blocks
@@ -321,6 +322,29 @@ int32_t fb_linearize(fb_handle h, const double* params, double* trim_state, int3
  * (fb_params block or fb_set_env rows, as fb_f_ode): FP/linearization.jl:55-111. Changes nothing on the handle. */
 int32_t fb_linearize_state(fb_handle h, int32_t scheme, double* xdot0, double* x0, double* u0, double* y0,
                            double* A, double* B, double* C, double* D, int32_t* lin_status);
+
+/* ---- Model(lss): LinearizedSS as a model (FB_MODEL_LSS; FP/linearization.jl:157-192) -------------------------------------------------
+ * A batch of N linear systems xdot = xdot0 + A (x - x0) + B (u - u0), y = y0 + C (x - x0) + D (u - u0), each with its own matrices, all
+ * with one (nx, nu, ny): 1 <= nx <= 32, 1 <= nu <= 8, 1 <= ny <= 64 (Robot2D 4 / 1 / 6, Cessna172Sv0 16 / 4 / 33, Cessna172Xv2 20 / 4 / 38 and
+ * every subsystem of them); FB_F64 only. The generic verbs serve such a handle: fb_size, fb_dims (Ns = 0), fb_set_state / fb_assign_state /
+ * fb_get_state (x [N x nx], s unused), fb_set_inputs / fb_get_inputs (u [N x nu], ui NULL), fb_f_ode (xdot [N x nx] and the record),
+ * fb_get_outputs (y [N x ny]), fb_step (RK4, u held over the call), fb_set_steps_per_launch, fb_set_params / fb_get_params (dt; the
+ * rest is unused), fb_time, fb_sync, fb_set_stream, fb_status (a linear model throws nothing: zeros), fb_get_step_count /
+ * fb_set_step_count, fb_timing_*, fb_log_* (output rows [0, ny), FB_LOG_X0 + state row), fb_destroy. fb_f_step and fb_f_periodic return 0
+ * and do nothing (@no_step, @no_periodic, :161-162). Verbs of other model families (trim, environment, tables, control laws, scenarios,
+ * linearize, RCCL gather, attach) fail with a message that names LinearizedSS. */
+/* Model(lss) for N systems of dimensions (nx, nu, ny) on device_id; the model comes from fb_lss_set_model. FC/modeling.jl:103-153 */
+int32_t fb_lss_create(int32_t nx, int32_t nu, int32_t ny, int64_t n, int32_t device_id, fb_handle* out);
+/* the LinearizedSS of every system (FP/linearization.jl:39-48), host arrays in exactly the layout fb_linearize writes them. Leaves
+ * x = x0 and u = u0 (Modeling.X(lss) = copy(lss.x0), Modeling.U(lss) = copy(lss.u0), :157-158), t = 0 and the step count 0. */
+int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, const double* u0, const double* y0,
+                         const double* A, const double* B, const double* C, const double* D);
+/* Model(subsystem(lss; x, u, y)) (FP/linearization.jl:113-132) device to device: lss = the result of src's last fb_linearize or
+ * fb_linearize_state, which is still on src's device (every block must have been requested in that call); ix [nx], iu [nu], iy [ny] = the rows
+ * and columns to keep, in the order given (NULL: every index in order, the count argument is then ignored). The new handle is on src's
+ * device (and on src's stream when that is the caller's own), takes src's dt, and starts at x = x0, u = u0, t = 0. */
+int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, const int32_t* iu, int32_t nu,
+                                  const int32_t* iy, int32_t ny, fb_handle* out);
 
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
