@@ -2,6 +2,7 @@
 // One handle = one HIP device + one stream + SoA device buffers. No CPU fallback: every compute entry
 // point launches a kernel; fb_create fails loudly when no HIP device is present.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -14,6 +15,7 @@
 #include "scenario_kernels.hpp"
 #include "lin_kernels.hpp"
 #include "lss_kernels.hpp"
+#include "lqr_kernels.hpp"
 
 using namespace fbd;
 
@@ -212,6 +214,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 #include "fb_robot2d.inc"
 #include "fb_log.inc"
 #include "fb_lss.inc"
+#include "fb_lqr.inc"
 struct ncclUniqueIdBlob { char internal[128]; };   // ncclUniqueId (rccl.h:40-43), passed by value
 
 // The scratch rows of the stepping kernels (ctl_bak, duo_pld, duo_tap) are zeroed when a handle is created: hipMalloc hands out zero pages in

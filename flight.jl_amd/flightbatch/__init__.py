@@ -16,3 +16,4 @@ from . import scenario  # noqa: F401
 from .fleet import MixedFleet  # noqa: F401
 from .linearization import LinearizedSS, linearize, linearize_state, subsystem, delete_vars  # noqa: F401
 from .lss import LinearWorld, linear_world  # noqa: F401
+from .lqr import LqrResult, lqr, closed_loop, design_model  # noqa: F401

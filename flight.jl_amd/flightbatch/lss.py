@@ -93,6 +93,12 @@ class LinearWorld(BatchedWorld):
         check(lib.fb_get_outputs(self._h, _pd(y)))
         return y
 
+    def model(self):
+        """(A [n, nx, nx], B [n, nx, nu]): the handle's own copy of the model, the matrices the device steps and designs on (read-only)"""
+        A, B = np.empty(self.nx * self.nx * self.n), np.empty(self.nx * self.nu * self.n)
+        check(lib.fb_lss_get_model(self._h, _pd(A), _pd(B)))
+        return unpack_matrix(A, self.nx, self.nx), unpack_matrix(B, self.nx, self.nu)
+
     def f_ode(self, xdot: np.ndarray | None = None) -> np.ndarray | None:
         """f_ode!(mdl): refreshes y on the device; with `xdot` ([nx, n]) also returns the derivative"""
         check(lib.fb_f_ode(self._h, _pd(xdot) if xdot is not None else None))

@@ -278,6 +278,24 @@ function linear_world(w::BatchedWorld; ix = nothing, iu = nothing, iy = nothing)
                 w.handle, arg(ix, jx), length(jx), arg(iu, ju), length(ju), arg(iy, jy), length(jy), h))
     return LinearWorld(h[])
 end
+"`lqr(P, Q, R)` (FA design/c172/c172x_design.jl:181) for every system of `w`, on its device: Q (nx x nx) and R (nu x nu) are the batch's,
+symmetric, R positive definite. Returns k (N x nu x nx), x (N x nx x nx), resid, iters, status (0, or FB_LQR_NOT_CONVERGED = 1 |
+FB_LQR_SINGULAR = 2: K, X and resid are NaN there)."
+function lqr(w::LinearWorld, q::Matrix{Float64}, r::Matrix{Float64})
+    size(q) == (w.nx, w.nx) || throw(DimensionMismatch("Q must be nx x nx"))
+    size(r) == (w.nu, w.nu) || throw(DimensionMismatch("R must be nu x nu"))
+    k = Array{Float64}(undef, w.n, w.nu, w.nx); x = Array{Float64}(undef, w.n, w.nx, w.nx)
+    resid = Vector{Float64}(undef, w.n); iters = Vector{Int32}(undef, w.n); status = Vector{Int32}(undef, w.n)
+    check(ccall((:fb_lqr, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}),
+                w.handle, q, r, k, x, resid, iters, status))
+    return (; k, x, resid, iters, status)
+end
+"A (N x nx x nx) and B (N x nx x nu) of the handle's own copy of the model: the matrices the device steps and designs on"
+function model(w::LinearWorld)
+    a = Array{Float64}(undef, w.n, w.nx, w.nx); b = Array{Float64}(undef, w.n, w.nx, w.nu)
+    check(ccall((:fb_lss_get_model, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), w.handle, a, b))
+    return (; a, b)
+end
 f_ode!(w::LinearWorld) = (check(ccall((:fb_f_ode, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, C_NULL)); nothing)
 f_step!(w::LinearWorld) = nothing        # @no_step LinearizedSS
 f_periodic!(w::LinearWorld) = nothing    # @no_periodic LinearizedSS

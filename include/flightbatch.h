@@ -345,6 +345,23 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
  * device (and on src's stream when that is the caller's own), takes src's dt, and starts at x = x0, u = u0, t = 0. */
 int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, const int32_t* iu, int32_t nu,
                                   const int32_t* iy, int32_t ny, fb_handle* out);
+/* the handle's own copy of the model, as its kernels read it: A [nx x nx] and B [nx x nu] of every system, host arrays in fb_linearize's
+ * layout (either may be NULL). Changes nothing on the handle. */
+int32_t fb_lss_get_model(fb_handle h, double* A, double* B);
+
+/* ---- lqr(P, Q, R) on a Model(lss) batch (FA design scripts: design/c172/c172x_design.jl:181 `lqr(P, Q, R)`, also :369, :475, :588, :651;
+ * design/robot2d/robot2d_design.jl:58) -------------------------------------------------------------------------------------------------
+ * For every system of an FB_MODEL_LSS handle with 1 <= nx <= FB_LQR_NX_MAX: the stabilising solution X of A'X + XA - X B inv(R) B' X + Q = 0 and
+ * the gain K = inv(R) B' X, by the matrix sign function of the Hamiltonian (Newton's iteration with determinant scaling, at most 50
+ * iterations; docs/design/linearize.md, "LQR design on the device"). Q [nx x nx] and R [nu x nu] are column-major host arrays, one pair for
+ * the batch: both symmetric (compared exactly), R positive definite. Outputs are host arrays, any may be NULL: element (i, r, c) of
+ * K [nu x nx] at K[(r + nu c) N + i], of X [nx x nx] at X[(r + nx c) N + i] (fb_linearize's layout); resid [N] = max|A'X + XA - XGX + Q| /
+ * max(max|Q|, max|X|); iters [N] = Newton iterations taken; status [N] = 0 or FB_LQR_* bits. A system with a non-zero status has K, X and
+ * resid = NaN; the call still returns 0. Reads A and B from the handle's copy of the model and changes nothing on the handle. */
+enum { FB_LQR_NOT_CONVERGED = 1,   /* the iteration bound was reached (eigenvalues of the Hamiltonian on or near the imaginary axis) */
+       FB_LQR_SINGULAR = 2,        /* a zero or non-finite pivot, or a non-finite result: no stabilising solution */
+       FB_LQR_NX_MAX = 16 };
+int32_t fb_lqr(fb_handle lss, const double* Q, const double* R, double* K, double* X, double* resid, int32_t* iters, int32_t* status);
 
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
