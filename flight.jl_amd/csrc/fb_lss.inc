@@ -213,6 +213,14 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
     return rc;
 }
 
+int32_t fb_lss_exchange(fb_handle h, int32_t* xch) {
+    if (!h) return fail("fb_lss_exchange: null handle");
+    if (!is_lss(h)) return fail("fb_lss_exchange: the handle is not a LinearizedSS handle (fb_lss_create, fb_lss_from_linearization)");
+    if (!xch) return fail("fb_lss_exchange: xch is null");
+    *xch = h->lss->xch;
+    return 0;
+}
+
 int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, const int32_t* iu, int32_t nu, const int32_t* iy, int32_t ny, fb_handle* out) {
     if (!out) return fail("out is null");
     *out = nullptr;

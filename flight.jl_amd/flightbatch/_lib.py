@@ -54,6 +54,7 @@ def _load():
         "fb_lss_set_model": ([H, D, D, D, D, D, D, D, D], C.c_int32),
         "fb_lss_from_linearization": ([H, I32, C.c_int32, I32, C.c_int32, I32, C.c_int32, C.POINTER(H)], C.c_int32),
         "fb_lss_get_model": ([H, D, D], C.c_int32),
+        "fb_lss_exchange": ([H, I32], C.c_int32),
         "fb_lqr": ([H, D, D, D, D, D, I32, I32], C.c_int32),
         "fb_f_step": ([H], C.c_int32),
         "fb_f_periodic": ([H], C.c_int32),

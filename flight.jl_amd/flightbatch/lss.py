@@ -99,6 +99,13 @@ class LinearWorld(BatchedWorld):
         check(lib.fb_lss_get_model(self._h, _pd(A), _pd(B)))
         return unpack_matrix(A, self.nx, self.nx), unpack_matrix(B, self.nx, self.nu)
 
+    @property
+    def exchange(self) -> str:
+        """"panel" or "shfl": how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"""
+        xch = C.c_int32(-1)
+        check(lib.fb_lss_exchange(self._h, C.byref(xch)))
+        return ("panel", "shfl")[xch.value]
+
     def f_ode(self, xdot: np.ndarray | None = None) -> np.ndarray | None:
         """f_ode!(mdl): refreshes y on the device; with `xdot` ([nx, n]) also returns the derivative"""
         check(lib.fb_f_ode(self._h, _pd(xdot) if xdot is not None else None))

@@ -296,6 +296,12 @@ function model(w::LinearWorld)
     check(ccall((:fb_lss_get_model, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), w.handle, a, b))
     return (; a, b)
 end
+"`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
+function exchange(w::LinearWorld)
+    xch = Ref{Int32}(-1)
+    check(ccall((:fb_lss_exchange, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), w.handle, xch))
+    return xch[] == 0 ? :panel : :shfl
+end
 f_ode!(w::LinearWorld) = (check(ccall((:fb_f_ode, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, C_NULL)); nothing)
 f_step!(w::LinearWorld) = nothing        # @no_step LinearizedSS
 f_periodic!(w::LinearWorld) = nothing    # @no_periodic LinearizedSS

@@ -345,6 +345,10 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
  * device (and on src's stream when that is the caller's own), takes src's dt, and starts at x = x0, u = u0, t = 0. */
 int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, const int32_t* iu, int32_t nu,
                                   const int32_t* iy, int32_t ny, fb_handle* out);
+/* how the handle's stepper exchanges the stage values inside a group of lanes: *xch = 0 the LDS panel (the default), 1 cross-lane reads
+ * (FLIGHTBATCH_LSS_EXCHANGE=shfl in the environment when the handle was created; the two give the same bits: docs/design/linearize.md).
+ * Works before a model is set; changes nothing on the handle. */
+int32_t fb_lss_exchange(fb_handle h, int32_t* xch);
 /* the handle's own copy of the model, as its kernels read it: A [nx x nx] and B [nx x nu] of every system, host arrays in fb_linearize's
  * layout (either may be NULL). Changes nothing on the handle. */
 int32_t fb_lss_get_model(fb_handle h, double* A, double* B);

@@ -5,7 +5,8 @@
   2. the reference's stored LQR gain tables of the Cessna172Xv2 autopilot, redesigned from the device's Jacobians at the 28 nodes;
   3. the same quotients formed on the host from fb_f_ode, point for point, off trim;
   4. the oracle's f_ode under the same scheme;
-plus the verb's effect on the handle, its refusals, the status bits and batch-size invariance."""
+plus the verb's effect on the handle, its refusals, the status bits and batch-size invariance; Robot2D on distinct robots under both
+schemes (the reference held to the oracle's f_ode), partial block requests, and inputs at the bounds of their Ranged types."""
 import ctypes as C
 
 import numpy as np
@@ -308,3 +309,254 @@ def test_batch_size_invariance(fb):
     for k in ("xdot0", "x0", "u0", "y0", "A", "B", "C", "D", "status", "success", "cost"):
         assert np.array_equal(getattr(small, k), getattr(big, k)[pick]), k
     ws.close()
+
+
+# ---- 9. Robot2D on distinct robots, both schemes ------------------------------------------------------------------------------------
+BLOCKS = ("xdot0", "x0", "u0", "y0", "A", "B", "C", "D")
+R2_N = 130
+# A's rows 2, 3 (θ̇ = ω, η̇ = v) and C | D's rows 0-4 (y = ω, v, θ, η, u_m) are differences of exact copies of the perturbed components, all
+# below 2 in magnitude here. FORWARD: fl(z + h) - z is exact, so the error is the rounding of z + h, <= 2^-53, over h >= 2^-26, plus the
+# quotient's own rounding: <= 2^-26 for two ulp of 1 over h. ONESIDED2: z + h is exact by construction; -3 z, its sum with 4 (z + h) and
+# fl(z + 2h) round below 8, 4 and 2: <= 2^-51 + 2^-52 + 2^-53 < 2^-50, over 2h >= 2e-6.
+R2_EXACT_TOL = {"forward": 2.0 ** -26, "onesided2": 2.0 ** -50 / 2e-6}
+
+
+def _r2_states(n=R2_N, seed=13):
+    """rows 0-4 of n state records: ω, v, θ, η and the motor input u_m, every robot its own"""
+    rng = np.random.default_rng(seed)
+    return np.vstack([rng.uniform(-s, s, n) for s in (0.5, 0.5, 0.5, 1.0, 0.8)])
+
+
+def _r2_world(fb, z):
+    w = fb.Robot2DWorld(z.shape[1])
+    fb.f_init(w, fb.InitParameters())
+    x = w.x
+    x[:5] = z
+    w.x = x
+    return w
+
+
+def _r2_host_linearize(fb, oracle, x, scheme):
+    """the scheme applied on the host to fb_f_ode of a second Robot2D handle, which is first held to the oracle's f_ode at every point:
+    xdot0 [n, 4], y0 [n, 6], A|B [n, 4, 5], C|D [n, 6, 5]"""
+    from test_oracle_robot2d import DEFAULT_VP
+    n = x.shape[1]
+    z = x[:5]
+    if scheme == "forward":
+        H = np.maximum(SQRT_EPS * np.abs(z), SQRT_EPS)
+        mult = (1.0,)
+    else:
+        H = (z + 1e-6 * np.maximum(np.abs(z), 1.0)) - z
+        mult = (1.0, 2.0)
+    npt = 1 + 5 * len(mult)
+    m = n * npt
+    X = np.repeat(x[:, None, :], npt, axis=1)
+    for j in range(5):
+        for p, c in enumerate(mult):
+            X[j, 1 + j * len(mult) + p] = z[j] + H[j] if c == 1.0 else z[j] + 2.0 * H[j]
+    X = np.ascontiguousarray(X.reshape(10, m))
+    w2 = fb.Robot2DWorld(m)
+    w2.x = X
+    xd = np.zeros((4, m))
+    fb.f_ode(w2, xd)
+    Y = w2.y
+    w2.close()
+    _D = C.POINTER(C.c_double)
+    xdo, vp = np.zeros((4, m)), DEFAULT_VP.copy()
+    oracle.lib.fo_robot2d_f_ode(C.c_int64(m), vp.ctypes.data_as(_D), X.ctypes.data_as(_D), xdo.ctypes.data_as(_D))
+    pre = np.max(np.abs(xd - xdo) / np.maximum(np.abs(xdo), 1.0))
+    assert pre < 1e-12, f"precondition: fb_f_ode is {pre:.3e} from the oracle's f_ode at the points of the reference"
+    f = np.vstack([xd, Y[:6]]).reshape(10, npt, n)
+    f0 = f[:, 0]
+    J = np.zeros((10, 5, n))
+    for j in range(5):
+        if scheme == "forward":
+            J[:, j] = (f[:, 1 + j] - f0) / H[j]
+        else:
+            J[:, j] = (-3.0 * f0 + 4.0 * f[:, 1 + 2 * j] - f[:, 2 + 2 * j]) / (2.0 * H[j])
+    return f0[:4].T, f0[4:].T, J[:4].transpose(2, 0, 1), J[4:].transpose(2, 0, 1)
+
+
+def _clock(fb, w):
+    cnt = C.c_int64(-1)
+    assert fb.lib.fb_get_step_count(w._h, C.byref(cnt)) == 0
+    return float(fb.lib.fb_time(w._h)), cnt.value
+
+
+@pytest.mark.parametrize("scheme", ["forward", "onesided2"])
+def test_robot2d_linearize_state_on_distinct_robots(fb, oracle, scheme, capsys):
+    n = R2_N
+    z = _r2_states()
+    w = _r2_world(fb, z)
+    x_before, u_before, st_before, clock_before = w.x, w.u, w.status, _clock(fb, w)
+    lss = fb.linearize_state(w, scheme=scheme)
+    assert np.array_equal(w.x, x_before) and np.array_equal(w.u, u_before) and np.array_equal(w.status, st_before) and _clock(fb, w) == clock_before
+    assert (lss.status == 0).all() and lss.A.shape == (n, 4, 4) and lss.B.shape == (n, 4, 1) and lss.C.shape == (n, 6, 4) and lss.D.shape == (n, 6, 1)
+    # x0 / u0: exactly the mapped rows; ẋ0 / y0: fb_f_ode's bits
+    assert np.array_equal(lss.x0, z[:4].T) and np.array_equal(lss.u0, z[4:].T)
+    xd = np.zeros((4, n))
+    fb.f_ode(w, xd)
+    assert np.array_equal(lss.xdot0, xd.T) and np.array_equal(lss.y0, w.y[:6].T)
+    xd0, y0, AB, CD = _r2_host_linearize(fb, oracle, x_before, scheme)
+    assert np.array_equal(lss.xdot0, xd0) and np.array_equal(lss.y0, y0)
+    tol = 1e-9 if scheme == "onesided2" else 1e-6
+    errs = {k: _scaled_err(got, want) for k, got, want in (("A", lss.A, AB[:, :, :4]), ("B", lss.B, AB[:, :, 4:]),
+                                                          ("C", lss.C, CD[:, :, :4]), ("D", lss.D, CD[:, :, 4:]))}
+    # what the reference's model fixes
+    I4 = np.eye(4)
+    exact = max(np.abs(lss.A[:, 2:] - I4[:2]).max(), np.abs(lss.C[:, :4] - I4).max(), np.abs(lss.D[:, :4]).max(),
+                np.abs(lss.C[:, 4]).max(), np.abs(lss.D[:, 4] - 1.0).max())
+    with capsys.disabled():
+        print(f"\n[Robot2D {scheme}] A B C D vs host quotients of fb_f_ode: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items())
+              + f"; fixed entries within {exact:.1e} (bound {R2_EXACT_TOL[scheme]:.1e})", end="")
+    assert all(v <= tol for v in errs.values()), errs
+    assert exact <= R2_EXACT_TOL[scheme]
+    # neighbours differ (a lane that read another robot's row or column would show against the host, and this is why)
+    assert np.abs(lss.A[1:, :2] - lss.A[:-1, :2]).reshape(n - 1, -1).max(axis=1).min() > 0
+    w.close()
+    # the first robots alone: the same bits (a lone lane, a partial wave)
+    for k in (1, 63):
+        ws = _r2_world(fb, z[:, :k])
+        sub = fb.linearize_state(ws, scheme=scheme)
+        for b in BLOCKS + ("status",):
+            assert np.array_equal(getattr(sub, b), getattr(lss, b)[:k]), (k, b)
+        ws.close()
+
+
+@pytest.mark.parametrize("scheme", ["forward", "onesided2"])
+def test_robot2d_linearize_with_per_robot_init_parameters(fb, scheme):
+    n = R2_N
+    rng = np.random.default_rng(17)
+    ip = fb.InitParameters(u_m=rng.uniform(-0.2, 0.2, n), ω=rng.uniform(-0.05, 0.05, n), η=rng.uniform(-1, 1, n))
+    w, ref = fb.Robot2DWorld(n), fb.Robot2DWorld(n)
+    lss = fb.linearize(w, ip, scheme=scheme)
+    fb.f_init(ref, ip)
+    # the world is left as f_init leaves it
+    assert np.array_equal(w.x, ref.x) and np.array_equal(w.u, ref.u) and np.array_equal(w.status, ref.status) and _clock(fb, w) == _clock(fb, ref)
+    assert np.array_equal(w.x[4], ip.pack(n)[0]) and np.array_equal(w.x[0], ip.pack(n)[1]) and np.array_equal(w.x[3], ip.pack(n)[2])
+    want = fb.linearize_state(ref, scheme=scheme)
+    for b in BLOCKS + ("status",):
+        assert np.array_equal(getattr(lss, b), getattr(want, b)), b
+    assert np.abs(lss.B[1:] - lss.B[:-1]).max() > 0 or np.abs(lss.A[1:] - lss.A[:-1]).max() > 0
+    w.close(); ref.close()
+
+
+# ---- 10. partial block requests --------------------------------------------------------------------------------------------------------
+SENTINEL = -7.25e77
+REQUESTS = (("A", "B"), ("C", "D"), ("xdot0", "x0", "u0", "y0"), ("B", "C"))
+
+
+def _raw_linearize_state(fb, w, scheme, want=BLOCKS):
+    """fb_linearize_state with NULL for every block not in `want`; the host buffers start as the sentinel. Returns them and the status."""
+    from flightbatch.linearization import dims
+    nx, nu, ny = dims(w)
+    n = w.n
+    size = dict(xdot0=nx, x0=nx, u0=nu, y0=ny, A=nx * nx, B=nx * nu, C=ny * nx, D=ny * nu)
+    b = {k: np.full(size[k] * n, SENTINEL) for k in BLOCKS}
+    st = np.full(n, -1, dtype=np.int32)
+    _D = C.POINTER(C.c_double)
+    ptrs = [b[k].ctypes.data_as(_D) if k in want else None for k in BLOCKS]
+    rc = fb.lib.fb_linearize_state(w._h, fb.K["FB_LIN_" + scheme.upper()], *ptrs, st.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0, fb.lib.fb_last_error()
+    for k in BLOCKS:
+        if k in want:
+            assert not (b[k] == SENTINEL).any() and np.isfinite(b[k]).all(), k        # written, every element
+        else:
+            assert (b[k] == SENTINEL).all(), k
+    return b, st
+
+
+def _batch_65(fb, robot):
+    return _r2_world(fb, _r2_states(65, seed=19)) if robot else _spread_trimmed(fb, False, 65, seed=23)
+
+
+@pytest.mark.parametrize("robot", [False, True], ids=["c172s0", "robot2d"])
+@pytest.mark.parametrize("scheme", ["forward", "onesided2"])
+def test_partial_block_requests_give_the_full_calls_bits(fb, robot, scheme):
+    w = _batch_65(fb, robot)
+    full, st_full = _raw_linearize_state(fb, w, scheme)
+    assert (st_full >= 0).all()
+    for want in REQUESTS:
+        part, st = _raw_linearize_state(fb, w, scheme, want)
+        assert np.array_equal(st, st_full), want
+        for k in want:
+            assert np.array_equal(part[k], full[k]), (want, k)
+    # and the Python route's reshaping agrees with the raw blocks
+    lss = fb.linearize_state(w, scheme=scheme)
+    n, nx = w.n, lss.x0.shape[1]
+    assert np.array_equal(lss.A, full["A"].reshape(nx, nx, n).transpose(2, 1, 0)) and np.array_equal(lss.x0, full["x0"].reshape(nx, n).T)
+    w.close()
+
+
+@pytest.mark.parametrize("robot", [False, True], ids=["c172s0", "robot2d"])
+def test_onesided2_after_forward_on_one_handle(fb, robot):
+    """the second call needs more room on the device than the first left (the first points' results of the Cessnas)"""
+    w, fresh = _batch_65(fb, robot), _batch_65(fb, robot)
+    assert np.array_equal(w.x, fresh.x) and np.array_equal(w.u, fresh.u)
+    _raw_linearize_state(fb, w, "forward", ("B",))
+    got, st = _raw_linearize_state(fb, w, "onesided2")
+    want, st_want = _raw_linearize_state(fb, fresh, "onesided2")
+    assert np.array_equal(st, st_want)
+    for k in BLOCKS:
+        assert np.array_equal(got[k], want[k]), k
+    # and back: the larger buffer serves the smaller request
+    back, _ = _raw_linearize_state(fb, w, "forward")
+    first, _ = _raw_linearize_state(fb, fresh, "forward")
+    for k in BLOCKS:
+        assert np.array_equal(back[k], first[k]), k
+    w.close(); fresh.close()
+
+
+# ---- 11. inputs at the bounds of their Ranged types --------------------------------------------------------------------------------
+AT_BOUND = (3, 40, 17, 63, 21)   # lanes: throttle 1, throttle 1, throttle 0, elevator -1, aileron half a step below 1
+
+
+@pytest.mark.parametrize("x2", [False, True], ids=["c172s0", "c172x2"])
+@pytest.mark.parametrize("scheme", ["onesided2", "forward"])
+def test_inputs_at_their_bounds(fb, x2, scheme, capsys):
+    n = 64
+    w = _spread_trimmed(fb, x2, n)
+    plain = fb.linearize_state(w, scheme=scheme)
+    h_nominal = SQRT_EPS if scheme == "forward" else 1e-6      # the step of either scheme for |z| <= 1
+    v = w.cs if x2 else w.u
+    rows = CS_ROWS if x2 else U_ROWS
+    v[rows[0], [3, 40]] = 1.0
+    v[rows[0], 17] = 0.0
+    v[rows[2], 63] = -1.0
+    v[rows[1], 21] = 1.0 - h_nominal / 2
+    if x2:
+        w.cs = v
+    else:
+        w.u = v
+    lss = fb.linearize_state(w, scheme=scheme)
+    assert lss.u0[3, 0] == 1.0 and lss.u0[40, 0] == 1.0 and lss.u0[17, 0] == 0.0 and lss.u0[63, 2] == -1.0 and lss.u0[21, 1] == 1.0 - h_nominal / 2
+    xd0, y0, AB, CD, z = _host_linearize(fb, x2, w, scheme)
+    nx = len(_abi_rows(x2))
+    assert np.array_equal(lss.x0, z[:nx].T) and np.array_equal(lss.u0, z[nx:].T)
+    tol = (1e-8 if x2 else 1e-9) if scheme == "onesided2" else 1e-6      # test_linearize_state_is_fb_f_ode_differenced's
+    errs = {k: _scaled_err(got, want) for k, got, want in (("A", lss.A, AB[:, :, :nx]), ("B", lss.B, AB[:, :, nx:]),
+                                                          ("C", lss.C, CD[:, :, :nx]), ("D", lss.D, CD[:, :, nx:]))}
+    at = list(AT_BOUND)
+    errs_at = {k: _scaled_err(got[at], want[at]) for k, got, want in (("B", lss.B, AB[:, :, nx:]), ("D", lss.D, CD[:, :, nx:]))}
+    with capsys.disabled():
+        print(f"\n[{'Xv2' if x2 else 'Sv0'} {scheme}, inputs at bounds] vs host quotients: " + "  ".join(f"{k} {v:.1e}" for k, v in errs.items())
+              + "; the five lanes at a bound: " + "  ".join(f"{k} {v:.1e}" for k, v in errs_at.items()), end="")
+    assert all(e <= tol for e in errs.values()), errs
+    # an input at its upper bound cannot be raised: every point is the baseline, and FORWARD's quotient (f(z) - f(z)) / h is exactly 0, on
+    # the host and on the device (ONESIDED2's -3 f + 4 f - f rounds, so its column is held to the host's above and no further)
+    if scheme == "forward":
+        for lane in (3, 40):
+            assert (AB[lane, :, nx] == 0).all() and (CD[lane, :, nx] == 0).all()
+            assert (lss.B[lane, :, 0] == 0.0).all() and (lss.D[lane, :, 0] == 0.0).all(), lane
+    # at a lower bound the step is free: the column is the host's and is not empty
+    for lane, k in ((17, 0), (63, 2)):
+        for got, want in ((lss.B[lane, :, k], AB[lane, :, nx + k]), (lss.D[lane, :, k], CD[lane, :, nx + k])):
+            assert np.abs(got - want).max() <= tol * max(np.abs(AB[lane]).max(), np.abs(CD[lane]).max())
+        assert np.abs(lss.B[lane, :, k]).max() > 0 and np.abs(lss.D[lane, :, k]).max() > 0
+    # half a step below the bound: the first point is clipped, the baseline is not, so the column is there but is not the free one
+    assert np.abs(lss.B[21, :, 1]).max() > 0 and not np.array_equal(lss.B[21, :, 1], plain.B[21, :, 1])
+    # the neighbours know nothing of it
+    others = np.setdiff1d(np.arange(n), AT_BOUND)
+    for k in BLOCKS + ("status",):
+        assert np.array_equal(getattr(lss, k)[others], getattr(plain, k)[others]), k
+    w.close()

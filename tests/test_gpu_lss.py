@@ -86,7 +86,7 @@ def test_reference_known_answer(fb, capsys):
 
 
 # ---- 2. shapes and edges ---------------------------------------------------------------------------------------------------------------
-SHAPES = [(1, 1, 1), (4, 1, 6), (5, 2, 3), (9, 3, 17), (16, 4, 33), (20, 4, 38), (32, 8, 64)]
+SHAPES = [(1, 1, 1), (4, 1, 6), (5, 2, 3), (8, 2, 3), (9, 3, 17), (16, 4, 33), (17, 4, 5), (20, 4, 38), (32, 8, 64)]
 
 
 @pytest.mark.parametrize("n", [1, 63, 130])
@@ -243,6 +243,71 @@ def test_device_to_device_construction(fb):
     with pytest.raises(fb.FlightBatchError, match="no linearisation has run"):
         fb.linear_world(r)
     r.close()
+
+
+# every source model, both exchanges (k_lss_gather's index arithmetic with snx = 20 and snx = 4; fb_lss_from_linearization reads
+# FLIGHTBATCH_LSS_EXCHANGE as fb_lss_create does). Selections are given in an order that is not ascending.
+def _linearized_x2(fb):
+    n = 8
+    w = fb.Cessna172Xv2World(n, kinematics="NED")
+    tp = fb.TrimParameters(EAS=np.linspace(35.0, 55.0, n), h_e=np.linspace(300.0, 2500.0, n), flaps=np.array([0, 0, 0.5, 1.0, 0, 0.25, 0, 0]))
+    lss = fb.linearize(w, tp)
+    assert lss.success.all() and (lss.status == 0).all()
+    sel = dict(x=("r", "φ", "v_y", "p", "β_filt", "rud_p", "ail_p"), u=("rudder_cmd", "aileron_cmd"), y=("β", "p", "χ", "φ", "r", "ail_p"))
+    return w, lss, (20, 4, 38), sel, (7, 2, 6)
+
+
+def _linearized_robot2d(fb):
+    n = 8
+    rng = np.random.default_rng(29)
+    w = fb.Robot2DWorld(n)
+    lss = fb.linearize(w, fb.InitParameters(u_m=rng.uniform(-0.2, 0.2, n), ω=rng.uniform(-0.05, 0.05, n), η=rng.uniform(-1, 1, n)))
+    assert (lss.status == 0).all() and np.abs(lss.A[1:] - lss.A[:-1]).max() > 0
+    return w, lss, (4, 1, 6), dict(x=("θ", "ω"), u=("m",), y=("τ_m", "θ")), (2, 1, 2)
+
+
+@pytest.mark.parametrize("name", ["panel", "shfl"])
+@pytest.mark.parametrize("source", [_linearized_x2, _linearized_robot2d], ids=["c172x2", "robot2d"])
+def test_device_to_device_construction_from_every_source(fb, source, name):
+    from test_gpu_lss_instances import exchange
+    w, lss, full, sel, part = source(fb)
+    rng = np.random.default_rng(5)
+    with exchange(name):
+        wd, wh = fb.linear_world(w), fb.LinearWorld(lss)
+        assert wd.exchange == name and wh.exchange == name
+        assert (wd.nx, wd.nu, wd.ny) == full and wd.x_labels == lss.x_labels and wd.y_labels == lss.y_labels
+        assert np.array_equal(wd.x, lss.x0.T) and np.array_equal(wd.u, lss.u0.T)
+        xd = _same_bits_after_run(fb, wd, wh, rng)
+        assert np.abs(xd).max() > 0
+        wd.close(); wh.close()
+        sub = fb.subsystem(lss, **sel)
+        wd, wh = fb.linear_world(w, **sel), fb.LinearWorld(sub)
+        assert wd.exchange == name and wh.exchange == name
+        assert (wd.nx, wd.nu, wd.ny) == part and wd.x_labels == sel["x"] and wd.u_labels == sel["u"] and wd.y_labels == sel["y"]
+        assert np.array_equal(wd.x, sub.x0.T) and np.array_equal(wd.u, sub.u0.T)
+        A, B = wd.model()                      # the handle's own copy: the selected rows and columns, in the order given
+        assert np.array_equal(A, sub.A) and np.array_equal(B, sub.B)
+        _same_bits_after_run(fb, wd, wh, rng)
+        wd.close(); wh.close()
+    w.close()
+
+
+@pytest.mark.parametrize("missing", ["x0", "u0", "A | B", "C | D"])
+def test_a_block_the_last_linearisation_did_not_write_is_refused_by_name(fb, missing):
+    n, (nx, nu, ny) = 8, (4, 1, 6)
+    w = fb.Robot2DWorld(n)
+    size = dict(xdot0=nx, x0=nx, u0=nu, y0=ny, A=nx * nx, B=nx * nu, C=ny * nx, D=ny * nu)
+    b = {k: np.empty(size[k] * n) for k in size}
+    st = np.zeros(n, dtype=np.int32)
+    ptrs = [None if k in missing.split(" | ") else _pd(b[k]) for k in ("xdot0", "x0", "u0", "y0", "A", "B", "C", "D")]
+    assert fb.lib.fb_linearize_state(w._h, fb.K["FB_LIN_FORWARD"], *ptrs, st.ctypes.data_as(C.POINTER(C.c_int32))) == 0
+    import re
+    with pytest.raises(fb.FlightBatchError, match="did not write " + re.escape(missing) + " on the device"):
+        fb.linear_world(w)
+    # a full linearisation afterwards serves
+    fb.linearize_state(w)
+    fb.linear_world(w).close()
+    w.close()
 
 
 # ---- 6. logging ------------------------------------------------------------------------------------------------------------------------

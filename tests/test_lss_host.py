@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("fb_lss_create", "fb_lss_set_model", "fb_lss_from_linearization")
+NEW = ("fb_lss_create", "fb_lss_set_model", "fb_lss_from_linearization", "fb_lss_exchange")
 
 
 def test_new_symbols_are_declared_exported_and_bound(fb):
@@ -50,6 +50,8 @@ def test_fb_create_points_to_fb_lss_create(fb):
     # and the entry points that take a handle say so when they get none
     assert fb.lib.fb_lss_set_model(None, *([None] * 8)) != 0 and b"null handle" in fb.lib.fb_last_error()
     assert fb.lib.fb_lss_from_linearization(None, None, 0, None, 0, None, 0, C.byref(h)) != 0 and b"null handle" in fb.lib.fb_last_error()
+    xch = C.c_int32(7)
+    assert fb.lib.fb_lss_exchange(None, C.byref(xch)) != 0 and b"fb_lss_exchange" in fb.lib.fb_last_error() and xch.value == 7
 
 
 def test_packing_round_trips_the_abi_layout(fb):
@@ -74,3 +76,21 @@ def test_packing_round_trips_the_abi_layout(fb):
         v = b[key]
         assert v.shape == (rows, n) and v.flags.c_contiguous
         assert np.array_equal(v.reshape(-1)[np.arange(rows)[:, None] * n + np.arange(n)[None, :]], getattr(m, key).T)
+
+
+def test_lss_and_lqr_kernels_are_in_the_library(tmp_path_factory):
+    """the instances lss_with_group and the LQR dispatcher launch, with the scratch and LDS docs/design/linearize.md tabulates"""
+    import test_kernel_resources as kr
+    ks = kr.kernels.__wrapped__(tmp_path_factory)
+    where = "the table of instances is the docstring of tests/test_gpu_lss_instances.py: an instance added or removed gets its row there"
+    groups = (4, 8, 16, 32)
+    lds = {f"fbl::k_lss_rk4<{g}, {x}>": 2048 * (1 - x) for g in groups for x in (0, 1)}
+    lds.update({f"fbl::k_lss_f_ode<{g}>": 2048 for g in groups})
+    lds["fbl::k_lss_gather"] = 0
+    assert {k for k in ks if k.startswith("fbl::k_lss_")} == set(lds), where
+    lqr = {f"fbq::k_lqr<{g}>" for g in (8, 16, 32)}
+    assert {k for k in ks if k.startswith("fbq::k_lqr")} == lqr, where
+    for name in sorted(set(lds) | lqr):
+        assert ks[name]["scratch"] == 0, (name, ks[name], where)
+    for name, want in lds.items():
+        assert ks[name]["lds"] == want, (name, ks[name], where)
