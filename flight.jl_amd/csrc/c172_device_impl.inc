@@ -45,13 +45,53 @@ constexpr int SCALAR_KNOTS_MIN = 3;   // tables with at most this many knots are
 
 constexpr real PI = FBL(3.14159265358979323846);
 
+// ---- resident-capable constants -----------------------------------------------------------------------------------------------------
+// gfx950's VOP3 encoding takes no fp64 literal: an fp64 constant that is no inline constant is a register pair built by two moves, at
+// every use (the build runs without machine LICM, and why: __graft_entry__.py). A kernel that HAS registers to spare — role P of
+// k_step_duo, c172_kernels.hpp — keeps such constants resident for the whole launch instead. So the helpers below take their constants
+// from a PROVIDER, kc<ID>(K): the default provider KLit returns the literal KC<ID>::v and every caller that passes none compiles as it
+// always did; a resident provider (DuoK, c172_kernels.hpp) returns a register for the first NK ids and the literal for the rest.
+// THE ORDER OF THE IDS IS THE PRIORITY (moves saved per register pair, counted on the assembly by tools/loop_literals.py): first the
+// constants used at several inlined sites, then the series coefficients and unit factors of the straight-line path; constants that
+// appear only in rare branches (the ISA layers above 11 km, the library exp) are no ids at all. A value is defined ONCE, here, by the
+// expression the compiler folded at the use before (e.g. the reciprocal that -freciprocal-math makes of a division by a constant).
+enum {
+    // atan2_tab (four inlined sites in role P: latitude, longitude, the propeller's two flow angles), geoid_height
+    KC_AT_C3, KC_AT_C5, KC_AT_C7, KC_AT_C9, KC_HALF_PI, KC_TWO_PI, KC_PI, KC_GEOID_PER_RAD,
+    KC_SQRT_TINY,   // sqrt(): three sites (the geoid's cos(lat), the propeller's airspeed and its in-plane component)
+    // isa_data<true>: the troposphere, straight-line
+    KC_ISA_H11, KC_ISA_BETA0, KC_ISA_LNP, KC_ISA_CFRAC,
+    KC_LN_C3, KC_LN_C5, KC_LN_C7, KC_LN_C9, KC_LN_C11, KC_LN_C13, KC_LN_C15, KC_LN_C17, KC_LN_C19, KC_LN_C21,
+    KC_EXP_C3, KC_EXP_C4, KC_EXP_C5, KC_EXP_C6, KC_EXP_C7, KC_EXP_C8, KC_EXP_C9,
+    KC_HELPERS_END   // (the ids of rhs_duo's own constants follow: c172_duo_device.hpp)
+};
+template <int I> struct KC;
+#define FB_KC(id, expr) template <> struct KC<id> { static constexpr real v = (expr); }
+// ... and a constant the source DIVIDES by, which -freciprocal-math turns into a multiplication by the reciprocal: the resident value is
+// that reciprocal, x * (1 / den); the literal provider keeps the division as written, so that such a caller's code is what it always was
+#define FB_KC_RCP(id, expr) template <> struct KC<id> { static constexpr real den = (expr), v = 1 / den; }
+struct KLit {
+    template <int I> static constexpr bool resident() { return false; }
+    template <int I> FBD constexpr real get() const { return KC<I>::v; }
+};
+template <int I, class KP> FBD real kc(const KP& K) { return K.template get<I>(); }
+template <int I, class KP> FBD real kc_div(real x, const KP& K) {
+    if constexpr (KP::template resident<I>()) return x * K.template get<I>(); else return x / KC<I>::den;
+}
+FB_KC(KC_AT_C3, -1.0 / 3); FB_KC(KC_AT_C5, 1.0 / 5); FB_KC(KC_AT_C7, -1.0 / 7); FB_KC(KC_AT_C9, 1.0 / 9);
+FB_KC(KC_HALF_PI, FBL(1.5707963267948966)); FB_KC(KC_TWO_PI, 2 * PI); FB_KC(KC_PI, FBL(3.141592653589793));
+FB_KC(KC_GEOID_PER_RAD, 720 / PI);   // EGM96 grid cells per radian, both axes
+FB_KC(KC_SQRT_TINY, sizeof(real) == 8 ? 1e-290 : 0.0);   // (the fp64 form's floor; the fp32 form is the library's)
+static_assert(KC<KC_HALF_PI>::v == PI / 2 && KC<KC_GEOID_PER_RAD>::v == 1440 / (2 * PI), "one constant serves both uses");
+
 // fp64 square roots without the library's range scaling and special-case fix-up (9 instructions instead of 17; at one wave per
 // SIMD every instruction costs an issue slot): v_rsq_f64 seed, one coupled Goldschmidt step on (g ~ sqrt x, h ~ 1/(2 sqrt x))
 // and one residual correction -> <= 1 ulp. Arguments here are sums of squares and physical magnitudes: 0 and NaN behave as in
 // sqrt() (0 -> 0, NaN -> NaN); numbers below 1e-290 are treated as 0.
-FBD real sqrt(real x) {
+template <class KP = KLit>
+FBD real sqrt(real x, const KP& K = KP{}) {
     if constexpr (sizeof(real) == 8) {
-        const double y = __builtin_amdgcn_rsq(__builtin_fmax((double)x, 1e-290));
+        const double y = __builtin_amdgcn_rsq(__builtin_fmax((double)x, (double)kc<KC_SQRT_TINY>(K)));
         double g = x * y, h = 0.5 * y;
         const double r = __builtin_fma(-h, g, 0.5);
         g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
@@ -81,7 +121,8 @@ FBD v3 operator-(v3 a) { return {-a.x, -a.y, -a.z}; }
 FBD v3 operator*(real s, v3 a) { return {s * a.x, s * a.y, s * a.z}; }
 FBD real dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 FBD v3 cross(v3 a, v3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-FBD real norm(v3 a) { return sqrt(dot(a, a)); }
+template <class KP = KLit>
+FBD real norm(v3 a, const KP& K = KP{}) { return sqrt(dot(a, a), K); }
 
 struct quat { real w, x, y, z; };
 FBD quat qmul(quat a, quat b) {
@@ -158,20 +199,20 @@ FBD void half_angle_cs(real y, real x, real& c, real& s) {
 // two s_mov each); error <= 1.6 ulp. atan2(0, 0) = 0; the sign of a zero x is not examined (atan2(0, -0) = 0, not π).
 // XPOS: the caller guarantees x >= 0 and (x, y) != (0, 0) (x is a norm next to a non-zero y, or the cosine of a latitude): the
 // x < 0 reflection and the atan2(0, 0) guard drop out.
-template <bool XPOS = false>
-FBD double atan2_tab(double y, double x, lds_cptr tab) {
+template <bool XPOS = false, class KP = KLit>
+FBD double atan2_tab(double y, double x, lds_cptr tab, const KP& K = KP{}) {
     const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
     const double mx = __builtin_fmax(ax, ay), mn = __builtin_fmin(ax, ay);
     const int i = (int)__builtin_rintf(((float)mn * __builtin_amdgcn_rcpf((float)mx)) * 32.0f);   // (NaN -> 0)
     const double ti = (double)i * (1.0 / 32);
     const double r = (mn - ti * mx) / (mx + ti * mn), s = r * r;
-    double p = __builtin_fma(s, 1.0 / 9, -1.0 / 7);
-    p = __builtin_fma(s, p, 1.0 / 5);
-    p = __builtin_fma(s, p, -1.0 / 3);
+    double p = __builtin_fma(s, (double)kc<KC_AT_C9>(K), (double)kc<KC_AT_C7>(K));
+    p = __builtin_fma(s, p, (double)kc<KC_AT_C5>(K));
+    p = __builtin_fma(s, p, (double)kc<KC_AT_C3>(K));
     double a = (double)tab[i] + __builtin_fma(r * s, p, r);
-    a = ay > ax ? FBL(1.5707963267948966) - a : a;
+    a = ay > ax ? kc<KC_HALF_PI>(K) - a : a;
     if constexpr (!XPOS) {
-        a = x < 0 ? FBL(3.141592653589793) - a : a;
+        a = x < 0 ? kc<KC_PI>(K) - a : a;
         a = mx > 0 ? a : 0.0;
     }
     return __builtin_copysign(a, y);
@@ -204,18 +245,21 @@ FBD real exp_step(real x) {
 FBD real log_step(real x) {
     if constexpr (sizeof(real) == 8) return log(x); else return __builtin_amdgcn_logf(x) * 0.6931471805599453f;
 }
-template <bool XPOS = false>
-FBD real atan2_step(real y, real x, lds_cptr tab) {   // the stepping kernels' atan2, by arithmetic type
-    if constexpr (sizeof(real) == 8) return atan2_tab<XPOS>(y, x, tab); else return atan2_fast<XPOS>(y, x);
+template <bool XPOS = false, class KP = KLit>
+FBD real atan2_step(real y, real x, lds_cptr tab, const KP& K = KP{}) {   // the stepping kernels' atan2, by arithmetic type
+    if constexpr (sizeof(real) == 8) return atan2_tab<XPOS>(y, x, tab, K); else return atan2_fast<XPOS>(y, x);
 }
 // log u for u near 1 (the troposphere's temperature ratio, 0.7 .. 1.1): 2 atanh w, w = (u - 1)/(u + 1), |w| < 0.18, ten series
 // terms; 45 instructions against the library's 98, error <= 1.5 ulp
-FBD double log_near1(double u) {
+FB_KC(KC_LN_C3, 2.0 / 3); FB_KC(KC_LN_C5, 2.0 / 5); FB_KC(KC_LN_C7, 2.0 / 7); FB_KC(KC_LN_C9, 2.0 / 9); FB_KC(KC_LN_C11, 2.0 / 11);
+FB_KC(KC_LN_C13, 2.0 / 13); FB_KC(KC_LN_C15, 2.0 / 15); FB_KC(KC_LN_C17, 2.0 / 17); FB_KC(KC_LN_C19, 2.0 / 19); FB_KC(KC_LN_C21, 2.0 / 21);
+template <class KP = KLit>
+FBD double log_near1(double u, const KP& K = KP{}) {
     const double w = (u - 1) / (u + 1), s = w * w;
-    double p = 2.0 / 21;
-    p = __builtin_fma(s, p, 2.0 / 19); p = __builtin_fma(s, p, 2.0 / 17); p = __builtin_fma(s, p, 2.0 / 15);
-    p = __builtin_fma(s, p, 2.0 / 13); p = __builtin_fma(s, p, 2.0 / 11); p = __builtin_fma(s, p, 2.0 / 9);
-    p = __builtin_fma(s, p, 2.0 / 7); p = __builtin_fma(s, p, 2.0 / 5); p = __builtin_fma(s, p, 2.0 / 3);
+    double p = kc<KC_LN_C21>(K);
+    p = __builtin_fma(s, p, (double)kc<KC_LN_C19>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C17>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C15>(K));
+    p = __builtin_fma(s, p, (double)kc<KC_LN_C13>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C11>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C9>(K));
+    p = __builtin_fma(s, p, (double)kc<KC_LN_C7>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C5>(K)); p = __builtin_fma(s, p, (double)kc<KC_LN_C3>(K));
     return __builtin_fma(w * s, p, w + w);
 }
 
@@ -250,11 +294,11 @@ FBD void sincos_step(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
 // Bilinear on the uniform grid lat ∈ [-π/2, π/2] (721), lon ∈ [0, 2π] (1441), linear extrapolation.
 // the EGM96 cell a point fell into: grid indices, fractional grid coordinates and the four samples
 struct GeoidCell { int i, j; real xi, xj, a00, a10, a01, a11; };
-template <bool FAST = false>
-FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon, GeoidCell& gc) {
+template <bool FAST = false, class KP = KLit>
+FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon, GeoidCell& gc, const KP& K = KP{}) {
     if constexpr (FAST) {
-        lat = atan2_step<true>(n.z, sqrt(n.x * n.x + n.y * n.y), T.rk + LDS_ATAN);   // (|n| ~ 1: never both zero)
-        lon = atan2_step(n.y, n.x, T.rk + LDS_ATAN);
+        lat = atan2_step<true>(n.z, sqrt(n.x * n.x + n.y * n.y, K), T.rk + LDS_ATAN, K);   // (|n| ~ 1: never both zero)
+        lon = atan2_step(n.y, n.x, T.rk + LDS_ATAN, K);
     } else {
         lat = atan2(n.z, sqrt(n.x * n.x + n.y * n.y));
         lon = atan2(n.y, n.x);
@@ -262,10 +306,10 @@ FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon, GeoidCell& gc
     // λ = mod(lon + 2π, 2π) (geodesy.jl:209) without calling fmod: lon ∈ [-π, π], so t = fl(lon + 2π) ∈ [π, 3π] and the
     // remainder is t itself or t - 2π, which is exact (Sterbenz). Branch-free on purpose: library fmod brings divergent
     // control flow into the stepping kernel, and with it the spill-placement bug tools/check_isa_spills.py guards against.
-    const real t2 = lon + 2 * PI;
-    const real lam = t2 >= 2 * PI ? t2 - 2 * PI : t2;
-    const real xi = (lat + PI / 2) * (720 / PI);
-    const real xj = lam * (1440 / (2 * PI));
+    const real t2 = lon + kc<KC_TWO_PI>(K);
+    const real lam = t2 >= kc<KC_TWO_PI>(K) ? t2 - kc<KC_TWO_PI>(K) : t2;
+    const real xi = (lat + kc<KC_HALF_PI>(K)) * kc<KC_GEOID_PER_RAD>(K);
+    const real xj = lam * kc<KC_GEOID_PER_RAD>(K);
     const int i = min(max((int)floor(xi), 0), 719);
     const int j = min(max((int)floor(xj), 0), 1439);
     const real wi = xi - i, wj = xj - j;
@@ -274,10 +318,10 @@ FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon, GeoidCell& gc
     gc = {i, j, xi, xj, a00, a10, a01, a11};
     return (1 - wi) * ((1 - wj) * a00 + wj * a01) + wi * ((1 - wj) * a10 + wj * a11);
 }
-template <bool FAST = false>
-FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon) {
+template <bool FAST = false, class KP = KLit>
+FBD real geoid_height(const Tables& T, v3 n, real& lat, real& lon, const KP& K = KP{}) {
     GeoidCell gc;
-    return geoid_height<FAST>(T, n, lat, lon, gc);
+    return geoid_height<FAST>(T, n, lat, lon, gc, K);
 }
 FBD real geoid_height(const Tables& T, v3 n) {
     real la, lo;
@@ -418,12 +462,14 @@ FBD loc grid_locate(lds_cptr k, lds_cptr rk, real x, bool flat_lo, bool flat_hi,
     return {i, (x - k[i]) * rk[i]};
 }
 // uniform knots a + j (b-a)/(n-1): a, b, n are literals at every call site, so the reciprocal step folds at compile time
-FBD loc range_locate(real a, real b, int n, real x, bool flat) {
+// (rstep: the reciprocal step (n - 1) / (b - a), for a caller that keeps it — and a, b — in registers: "resident-capable constants")
+FBD loc range_locate(real a, real b, real rstep, int n, real x, bool flat) {
     if (flat) x = fmin(fmax(x, a), b);
-    const real xi = (x - a) * ((n - 1) / (b - a));
+    const real xi = (x - a) * rstep;
     const int i = min(max((int)floor(xi), 0), n - 2);
     return {i, xi - i};
 }
+FBD loc range_locate(real a, real b, int n, real x, bool flat) { return range_locate(a, b, (n - 1) / (b - a), n, x, flat); }
 // Table values are read one ds_read_b64 each: left to itself the compiler pairs neighbouring elements into ds_read2_b64, and for
 // ONE wave per SIMD reading lane-dependent (scattered, bank-conflicting) addresses a ds_read2_b64 costs the wave 24-43 issue cycles
 // against 2 x 6-8 for two single reads (tools/microbench/lds.hip: bilinear corners as 2 x read2 +87 cycles, as 4 x read +25).
@@ -450,30 +496,36 @@ constexpr real isa_sqrt_T_std = FBL(16.97498159056439);   // sqrt(288.15)
 // lnp = log(p / p_sl), the sum of the layers' exponents (the engine model wants log(p / p_std) again, piston.jl:38-41).
 // The troposphere is evaluated straight-line for every lane (same arithmetic as the layer loop's first pass); the loop over
 // the higher layers is only entered above 11 km.
-template <bool FAST = false>
-FBD void isa_data(real h, real T_sl, real p_sl, real& T, real& p, real& lnp, int32_t& st) {
+FB_KC(KC_ISA_H11, 11000); FB_KC(KC_ISA_BETA0, -FBL(6.5e-3));
+FB_KC(KC_ISA_LNP, -isa::g_std / (-FBL(6.5e-3) * isa::R));            // the exponent of the troposphere's pressure law, 5.2559
+FB_KC(KC_ISA_CFRAC, -isa::g_std / (-FBL(6.5e-3) * isa::R) - 5);      // ... and what is left of it behind u0^5
+FB_KC(KC_EXP_C3, FBL(1.0) / 6); FB_KC(KC_EXP_C4, FBL(1.0) / 24); FB_KC(KC_EXP_C5, FBL(1.0) / 120); FB_KC(KC_EXP_C6, FBL(1.0) / 720);
+FB_KC(KC_EXP_C7, FBL(1.0) / 5040); FB_KC(KC_EXP_C8, FBL(1.0) / 40320); FB_KC(KC_EXP_C9, FBL(1.0) / 362880);
+template <bool FAST = false, class KP = KLit>
+FBD void isa_data(real h, real T_sl, real p_sl, real& T, real& p, real& lnp, int32_t& st, const KP& K = KP{}) {
     constexpr real beta[7] = {-FBL(6.5e-3), 0, FBL(1e-3), FBL(2.8e-3), 0, -FBL(2.8e-3), -FBL(2e-3)};
     constexpr real hc[7] = {11000, 20000, 32000, 47000, 51000, 71000, 84852};
-    const real h0 = fmin(h, hc[0]);
-    T = T_sl + beta[0] * h0;
-    const real u0 = 1 + beta[0] / T_sl * h0;
+    static_assert(KC<KC_ISA_H11>::v == hc[0] && KC<KC_ISA_BETA0>::v == beta[0] && KC<KC_ISA_LNP>::v == -isa::g_std / (beta[0] * isa::R), "the first layer's constants");
+    const real h0 = fmin(h, kc<KC_ISA_H11>(K));
+    T = T_sl + kc<KC_ISA_BETA0>(K) * h0;
+    const real u0 = 1 + kc<KC_ISA_BETA0>(K) / T_sl * h0;
     real ln_u0;
-    if constexpr (FAST && sizeof(real) == 8) ln_u0 = log_near1(u0); else if constexpr (FAST) ln_u0 = log_step(u0); else ln_u0 = log(u0);
-    lnp = -isa::g_std / (beta[0] * isa::R) * ln_u0;
+    if constexpr (FAST && sizeof(real) == 8) ln_u0 = log_near1(u0, K); else if constexpr (FAST) ln_u0 = log_step(u0); else ln_u0 = log(u0);
+    lnp = kc<KC_ISA_LNP>(K) * ln_u0;
     if constexpr (FAST && sizeof(real) == 8) {
         // p / p_sl = u0^c, c = g / (beta R) = 5.2559: u0^5 by multiplication, u0^(c - 5) = exp(y) with |y| = 0.256 |ln u0| < 0.1 straight from
         // the series (no range reduction, degree 9: 3e-17) — 15 arithmetic instructions instead of the library exp's ~40
-        constexpr real cfrac = -isa::g_std / (beta[0] * isa::R) - 5;
-        static_assert(cfrac > FBL(0.25) && cfrac < FBL(0.26), "the exponent of the troposphere's pressure law");
-        const real y = cfrac * ln_u0;
-        real e = FBL(1.0) / 362880;
-        e = __builtin_fma(e, y, FBL(1.0) / 40320); e = __builtin_fma(e, y, FBL(1.0) / 5040); e = __builtin_fma(e, y, FBL(1.0) / 720);
-        e = __builtin_fma(e, y, FBL(1.0) / 120); e = __builtin_fma(e, y, FBL(1.0) / 24); e = __builtin_fma(e, y, FBL(1.0) / 6);
+        constexpr real cfrac = KC<KC_ISA_CFRAC>::v;
+        static_assert(cfrac == -isa::g_std / (beta[0] * isa::R) - 5 && cfrac > FBL(0.25) && cfrac < FBL(0.26), "the exponent of the troposphere's pressure law");
+        const real y = kc<KC_ISA_CFRAC>(K) * ln_u0;
+        real e = kc<KC_EXP_C9>(K);
+        e = __builtin_fma(e, y, kc<KC_EXP_C8>(K)); e = __builtin_fma(e, y, kc<KC_EXP_C7>(K)); e = __builtin_fma(e, y, kc<KC_EXP_C6>(K));
+        e = __builtin_fma(e, y, kc<KC_EXP_C5>(K)); e = __builtin_fma(e, y, kc<KC_EXP_C4>(K)); e = __builtin_fma(e, y, kc<KC_EXP_C3>(K));
         e = __builtin_fma(e, y, FBL(0.5)); e = __builtin_fma(e, y, FBL(1.0)); e = __builtin_fma(e, y, FBL(1.0));
         const real u2 = u0 * u0, u4 = u2 * u2;
         p = (p_sl * (u4 * u0)) * e;
     } else if constexpr (FAST) p = p_sl * exp_step(lnp); else p = p_sl * exp(lnp);
-    if (h < hc[0]) return;
+    if (h < kc<KC_ISA_H11>(K)) return;
     real hb = hc[0], Tb = T, pb = p;
     bool done = false;
 #pragma unroll 1

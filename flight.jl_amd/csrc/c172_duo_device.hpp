@@ -64,8 +64,35 @@ constexpr int XD_VP = XD_FP;   // role D -> role P before barrier A: the velocit
 // rows of KArgs::duo_tap a tapped evaluation of the Cessna172Xv2 instance writes (the DUO_TAP_* enum of c172_kernels.hpp, which checks these)
 constexpr int DUO_TAP_THETA_ROW = 0, DUO_TAP_WX_ROW = 2, DUO_TAP_VD_ROW = 5, DUO_TAP_EAS_ROW = 7, DUO_TAP_ALPHA_ROW = 8, DUO_TAP_LAT_ROW = 10;
 
-template <int KIN, int ROLE, class In, class Emit, class XV>
-__device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state, const In& in, const Env& env, const Tables& T, const Emit& emit, StepAux& aux) {
+// Role P's own resident-capable constants (c172_device_impl.inc: "resident-capable constants"; the ids go on behind the helpers', in
+// the order of what a register pair saves): propeller, engine, air data. Each is the number the compiler folded at its use before.
+enum {
+    KC_P_PROP_HI = KC_HELPERS_END, KC_P_PROP_RSTEP,   // the propeller table's two axes: two sites each
+    KC_P_WGS_A, KC_P_PROP_RX, KC_P_PROP_RZ,           // two uses each
+    KC_P_INV_R, KC_P_INV_SQRT_GR, KC_P_INV_TWO_PI, KC_P_0P1, KC_P_PROP_JXX,
+    KC_P_FRC_KP, KC_P_FRC_KI, KC_P_INV_W_IDLE, KC_P_INV_W_RATED, KC_P_INV_P_STD,
+    KC_P_N2_LO, KC_P_N2_RSTEP, KC_P_D9_LO, KC_P_D9_RSTEP, KC_P_M9_LO, KC_P_M9_RSTEP,
+    KC_P_INV_RHO_STD, KC_P_F_DIFF, KC_P_F_RICH, KC_P_5EM3, KC_P_SQRT_T_STD, KC_P_P_RATED, KC_P_TAU_FRC, KC_P_INV_J, KC_P_INV_M_FUEL,
+    KC_P_F_LEAN,                                      // (its low word is zero: one literal move)
+    KC_COUNT
+};
+FB_KC(KC_P_PROP_HI, 1.5); FB_KC(KC_P_PROP_RSTEP, (PR_NJ - 1) / (1.5 - 0.0));
+static_assert(PR_NJ == PR_NM, "one reciprocal step serves both axes of the propeller table");
+FB_KC(KC_P_WGS_A, wgs::a); FB_KC(KC_P_PROP_RX, c172::prop_r[0]); FB_KC(KC_P_PROP_RZ, c172::prop_r[2]);
+FB_KC(KC_P_INV_R, 1 / isa::R); FB_KC(KC_P_INV_SQRT_GR, 1 / 20.046795704052055); FB_KC_RCP(KC_P_INV_TWO_PI, 2 * PI); FB_KC(KC_P_0P1, 0.1);
+FB_KC(KC_P_PROP_JXX, c172::prop_Jxx); FB_KC(KC_P_FRC_KP, 5.0); FB_KC(KC_P_FRC_KI, 200.0);
+FB_KC_RCP(KC_P_INV_W_IDLE, c172::w_idle); FB_KC_RCP(KC_P_INV_W_RATED, c172::w_rated); FB_KC_RCP(KC_P_INV_P_STD, isa::p_std);
+FB_KC(KC_P_N2_LO, 0.667); FB_KC(KC_P_N2_RSTEP, (2 - 1) / (1.0 - 0.667));
+FB_KC(KC_P_D9_LO, 0.441); FB_KC(KC_P_D9_RSTEP, (9 - 1) / (1.0 - 0.441));
+FB_KC(KC_P_M9_LO, 0.401); FB_KC(KC_P_M9_RSTEP, (9 - 1) / (0.936 - 0.401));
+FB_KC(KC_P_INV_RHO_STD, 1 / isa::rho_std); FB_KC(KC_P_F_DIFF, c172::f_rich - c172::f_lean); FB_KC(KC_P_F_RICH, c172::f_rich); FB_KC(KC_P_5EM3, 5e-3);
+FB_KC(KC_P_SQRT_T_STD, isa_sqrt_T_std); FB_KC(KC_P_P_RATED, c172::P_rated); FB_KC(KC_P_TAU_FRC, 0.01 * c172::P_rated / c172::w_rated);
+FB_KC_RCP(KC_P_INV_J, c172::J_eng + c172::prop_Jxx); FB_KC_RCP(KC_P_INV_M_FUEL, c172::m_full - c172::m_res);
+FB_KC(KC_P_F_LEAN, c172::f_lean);
+
+template <int KIN, int ROLE, class In, class Emit, class XV, class KP = KLit>
+__device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state, const In& in, const Env& env, const Tables& T, const Emit& emit, StepAux& aux,
+                                           const KP& K = KP{}) {   // K: role P's constants (role D passes none: literals)
     using namespace c172;
     static_assert(ROLE == 1 || ROLE == 2, "role P or role D");
     static_assert(KIN == FB_KIN_WA || KIN == FB_KIN_ECEF || KIN == FB_KIN_NED, "kinematic mechanisation");
@@ -73,8 +100,8 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
     constexpr int KX = FB_X_Q_WB;
     constexpr bool X = Emit::x2;   // Cessna172Xv2 (k_step_duo<KIN, true>): see the kernel's header
     auto gkp = [&](int off) -> gk_cptr { return T.gk + off; };
-    auto atan2m = [&](double y, double x0) -> double { return atan2_step(y, x0, T.rk + LDS_ATAN); };
-    auto atan2p = [&](double y, double x0) -> double { return atan2_step<true>(y, x0, T.rk + LDS_ATAN); };   // x0 >= 0, not both zero
+    auto atan2m = [&](double y, double x0) -> double { return atan2_step(y, x0, T.rk + LDS_ATAN, K); };
+    auto atan2p = [&](double y, double x0) -> double { return atan2_step<true>(y, x0, T.rk + LDS_ATAN, K); };   // x0 >= 0, not both zero
 
     // ===== kinematics head (kinematics.jl:181-223; geodesy.jl:62-69, 140-147). Role P needs the position only (n_e from q_ew, h_e); the
     // attitude products, the wind-relative velocity and from it the velocity at the propeller are role D's, which hands the latter over =====
@@ -125,7 +152,7 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         double lat, lon;
         // (gathered at every evaluation: a per-lane cache of the EGM96 cell gains 1.5 % for a fleet spread over the sphere and loses 0.5 % on a batch
         // that sits in one cell, profiles/r05_ab_geoid_cache.txt; the removed code is profiles/r07_duo_geoid_cache.patch)
-        const double h_o = h_e - geoid_height<true>(T, n_e, lat, lon);
+        const double h_o = h_e - geoid_height<true>(T, n_e, lat, lon, K);
         if (!(h_o >= H_MIN)) st |= FB_ST_ALT_RANGE;
         if constexpr (X) {
             if (emit.tap) {   // kinematics.y.ϕ_λ as the guidance reads it (rhs(): the states themselves in the NED mechanisation)
@@ -136,12 +163,11 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         // ----- air data (atmosphere.jl:220-242) -----
         DUO_MARK(1, 1);   // geoid done
         double T_air, p_air, lnp_air;
-        const double h_gp = h_o * wgs::a / (wgs::a + h_o);   // geopotential altitude
-        isa_data<true>(h_gp, env.T_sl, env.p_sl, T_air, p_air, lnp_air, st);
+        const double h_gp = h_o * kc<KC_P_WGS_A>(K) / (kc<KC_P_WGS_A>(K) + h_o);   // geopotential altitude
+        isa_data<true>(h_gp, env.T_sl, env.p_sl, T_air, p_air, lnp_air, st, K);
         const double rs_T = rsqrt(T_air), i_T = rs_T * rs_T;
-        const double rho = (p_air * (1 / isa::R)) * i_T;
-        constexpr double sqrt_gR = 20.046795704052055;   // sqrt(1.4 * 287.05287)
-        const double i_a_snd = (1 / sqrt_gR) * rs_T;
+        const double rho = (p_air * kc<KC_P_INV_R>(K)) * i_T;
+        const double i_a_snd = kc<KC_P_INV_SQRT_GR>(K) * rs_T;   // 1 / sqrt(1.4 * 287.05287 T)
         DUO_MARK(1, 2);   // ISA done
         emit.xput(XD_RHO, rho); emit.xput(XD_HO, h_o);
         DUO_MARK(1, 11);  // at A
@@ -152,11 +178,11 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         // ----- propeller (propellers.jl:405-452) -----
         const double w_prop = w_eng;  // gear ratio 1
         const v3 v_p = {emit.xget(XD_VP), emit.xget(XD_VP + 1), emit.xget(XD_VP + 2)};   // v_wb_b + w_eb_b x r_p, from role D
-        const double v_J = norm(v_p);
-        const double J_adv = 2 * PI * v_J / (fmax(fabs(w_prop), 1.0) * prop_d);
+        const double v_J = norm(v_p, K);
+        const double J_adv = kc<KC_TWO_PI>(K) * v_J / (fmax(fabs(w_prop), 1.0) * prop_d);
         const double Mt = fabs(w_prop) * (prop_d / 2) * i_a_snd;
-        const loc lj = range_locate(0.0, 1.5, PR_NJ, J_adv, true);
-        const loc lm = range_locate(0.0, 1.5, PR_NM, Mt, true);
+        const loc lj = range_locate(0.0, kc<KC_P_PROP_HI>(K), kc<KC_P_PROP_RSTEP>(K), PR_NJ, J_adv, true);
+        const loc lm = range_locate(0.0, kc<KC_P_PROP_HI>(K), kc<KC_P_PROP_RSTEP>(K), PR_NM, Mt, true);
         const double w00 = (1 - lj.w) * (1 - lm.w), w01 = (1 - lj.w) * lm.w, w10 = lj.w * (1 - lm.w), w11 = lj.w * lm.w;
         // (no LDS to spare for this 14 KB table: its four corner records come from the blob in global memory — hot in the vector L1 — as
         // one batch of loads)
@@ -166,74 +192,74 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         };
         const double C_Fx = coef(0), C_Mx = coef(1), C_Fz_a = coef(2), C_Mz_a = coef(3);
         double a_p = 0, b_p = 0;
-        if (!(v_J < 0.1)) {
+        if (!(v_J < kc<KC_P_0P1>(K))) {
             a_p = atan2m(v_p.z, v_p.x);
-            b_p = atan2p(v_p.y, sqrt(v_p.x * v_p.x + v_p.z * v_p.z));
+            b_p = atan2p(v_p.y, sqrt(v_p.x * v_p.x + v_p.z * v_p.z, K));
         }
         DUO_MARK(1, 4);   // propeller coefficients and angles
-        const double fr = w_prop / (2 * PI), fr2 = fr * fr;
+        const double fr = kc_div<KC_P_INV_TWO_PI>(w_prop, K), fr2 = fr * fr;
         constexpr double d4 = prop_d * prop_d * prop_d * prop_d, d5 = d4 * prop_d;
         const double kF = rho * fr2 * d4, kM = rho * fr2 * d5;
         const v3 F_p = {kF * C_Fx, kF * (C_Fz_a * b_p), kF * (C_Fz_a * a_p)};
         const v3 tau_p = {kM * C_Mx, kM * (C_Mz_a * b_p), kM * (C_Mz_a * a_p)};  // CW: sense = +1
-        const v3 tau_pb = tau_p + cross(r_p, F_p);
+        const v3 tau_pb = tau_p + cross(v3{kc<KC_P_PROP_RX>(K), prop_r[1], kc<KC_P_PROP_RZ>(K)}, F_p);
         emit.xput(XD_FP, F_p.x); emit.xput(XD_FP + 1, F_p.y); emit.xput(XD_FP + 2, F_p.z);
         emit.xput(XD_TAUP, tau_pb.x); emit.xput(XD_TAUP + 1, tau_pb.y); emit.xput(XD_TAUP + 2, tau_pb.z);
         DUO_MARK(1, 5);   // wrench put
-        emit.xput(XD_HROT, prop_Jxx * w_prop);
+        emit.xput(XD_HROT, kc<KC_P_PROP_JXX>(K) * w_prop);
         emit.xpub(DUO_PT_W);    // ----- point W: propeller wrench put -----
 
         // ----- engine (piston.jl:314-426) -----
         double out_frc, out_idle;
         static_assert(FB_X_ENG_FRC == FB_X_ENG_IDLE + 1, "engine regulator rows are adjacent");
-        const double kfrc = pi_ode(5.0, 200.0, 0.0, -1.0, 1.0, -w_eng, x_frc, out_frc);
-        const double ke2[2] = {pi_ode(4.0, 2.0, 0.0, -0.5, 0.5, 1 - w_eng / w_idle, x_idle, out_idle), kfrc};
+        const double kfrc = pi_ode(kc<KC_P_FRC_KP>(K), kc<KC_P_FRC_KI>(K), 0.0, -1.0, 1.0, -w_eng, x_frc, out_frc);
+        const double ke2[2] = {pi_ode(4.0, 2.0, 0.0, -0.5, 0.5, 1 - kc_div<KC_P_INV_W_IDLE>(w_eng, K), x_idle, out_idle), kfrc};
         emit_rows<2>(emit, FB_X_ENG_IDLE, ke2);
         const double mu_ratio_idle = 0.5 + out_idle;
-        const double n_eng = w_eng / w_rated;
+        const double n_eng = kc_div<KC_P_INV_W_RATED>(w_eng, K);
         const double rt_arg = (0.5 * 6.5e-3 * isa::R / isa::g_std) * (env.ln_p_sl + lnp_air);
-        const bool tropo = h_gp < 11000.0;
+        const bool tropo = h_gp < kc<KC_ISA_H11>(K);
         double rt_theta = env.k_rt * (T_air * rs_T);   // (T_ISA/T_std)^1/2, see rhs()
         if (__builtin_amdgcn_ballot_w64(!tropo) != 0) { const double e = exp_step(rt_arg); rt_theta = tropo ? rt_theta : e; }
-        const double delta = (p_air / isa::p_std) / rt_theta;
+        const double delta = kc_div<KC_P_INV_P_STD>(p_air, K) / rt_theta;
         const double throttle = in.get_throttle(), mixture = in.get_mixture();
-        const loc l_n2 = range_locate(0.667, 1.0, 2, n_eng, false);
-        const double mu_wot = lerp2(PT + PT_MU_WOT_V, 2, l_n2, range_locate(0.441, 1.0, 9, delta, false));
+        const loc l_n2 = range_locate(kc<KC_P_N2_LO>(K), 1.0, kc<KC_P_N2_RSTEP>(K), 2, n_eng, false);
+        const double mu_wot = lerp2(PT + PT_MU_WOT_V, 2, l_n2, range_locate(kc<KC_P_D9_LO>(K), 1.0, kc<KC_P_D9_RSTEP>(K), 9, delta, false));
         const double mu = mu_wot * (mu_ratio_idle + throttle * (1 - mu_ratio_idle));
 DUO_MARK(1, 6);   // engine head done
         // behind W role P has the longer way to go (the rest of the engine: ~400 instructions against role D's ~110 once it has the wrench): it
         // goes ahead of D in issue priority until its evaluation ends (profiles/r03_ab_prio.txt)
         constexpr int DUO_P_TAIL_PRIO = 3;
         __builtin_amdgcn_s_setprio(DUO_P_TAIL_PRIO);
-        const double k_f = rsqrt(rho * (1 / isa::rho_std));
+        const double k_f = rsqrt(rho * kc<KC_P_INV_RHO_STD>(K));
         const bool mix_auto = in.ui & FB_UI_MIXTURE_AUTO;
-        const double f_run = mix_auto ? f_lean + mixture * (f_rich - f_lean) : k_f * (f_rich * (0.5 * (mixture + 1)));
+        const double f_run = mix_auto ? kc<KC_P_F_LEAN>(K) + mixture * kc<KC_P_F_DIFF>(K) : k_f * (kc<KC_P_F_RICH>(K) * (0.5 * (mixture + 1)));
         const loc l_n13 = grid_locate<13, true, AUX_N13>(PT + PT_PISTD_N_K, RPT + PT_PISTD_N_K, n_eng, true, true, gkp(LDS_PISTON + PT_PISTD_N_K), T.gk);
         const loc l_n5w = grid_locate<5, true>(PT + PT_PIWOT_N_K, RPT + PT_PIWOT_N_K, n_eng, true, true, gkp(LDS_PISTON + PT_PIWOT_N_K));
         const loc l_n5s = grid_locate<5, true>(PT + PT_SFC_N_K, RPT + PT_SFC_N_K, n_eng, false, false, gkp(LDS_PISTON + PT_SFC_N_K));
         const loc l_f = grid_locate<11, true, AUX_F11>(PT + PT_F_K, RPT + PT_F_K, f_run, true, true, gkp(LDS_PISTON + PT_F_K), T.gk);
         const double pi_ratio = lerp1(PT + PT_PI_RATIO_V, l_f), sfc_ratio = lerp1(PT + PT_SFC_RATIO_V, l_f);
-        const double d_wot = lerp2(PT + PT_DELTA_WOT_V, 2, l_n2, range_locate(0.401, 0.936, 9, mu, false));
+        const double d_wot = lerp2(PT + PT_DELTA_WOT_V, 2, l_n2, range_locate(kc<KC_P_M9_LO>(K), 0.936, kc<KC_P_M9_RSTEP>(K), 9, mu, false));
         const double pi_std = lerp2(PT + PT_PISTD_V, 13, l_n13, grid_locate<3, true>(PT + PT_PISTD_MU_K, RPT + PT_PISTD_MU_K, mu, true, true, gkp(LDS_PISTON + PT_PISTD_MU_K)));
         const double pi_wot = lerp2(PT + PT_PIWOT_V, 5, l_n5w, grid_locate<3, true>(PT + PT_PIWOT_D_K, RPT + PT_PIWOT_D_K, d_wot, true, false, gkp(LDS_PISTON + PT_PIWOT_D_K)));
-        double pi_isa = (fabs(d_wot - 1) < 5e-3) ? pi_std : pi_std + (pi_wot - pi_std) / (d_wot - 1) * (delta - 1);
+        double pi_isa = (fabs(d_wot - 1) < kc<KC_P_5EM3>(K)) ? pi_std : pi_std + (pi_wot - pi_std) / (d_wot - 1) * (delta - 1);
         pi_isa = fmax(pi_isa, 0.0);
         DUO_MARK(1, 8);   // engine lookups
-        const double pi_pow = pi_isa * (rt_theta * (isa_sqrt_T_std * rs_T));   // pi_isa (T_ISA / T)^1/2
+        const double pi_pow = pi_isa * (rt_theta * (kc<KC_P_SQRT_T_STD>(K) * rs_T));   // pi_isa (T_ISA / T)^1/2
         const double pi_act = pi_pow * pi_ratio;
-        const double P_run = P_rated * pi_act;
+        const double P_run = kc<KC_P_P_RATED>(K) * pi_act;
         const double tau_run = (w_eng > 0) ? P_run / w_eng : 0.0;
         const double SFC_run = lerp2(PT + PT_SFC_POW_V, 5, l_n5s, grid_locate<8, true>(PT + PT_SFC_PI_K, RPT + PT_SFC_PI_K, pi_act, false, false, gkp(LDS_PISTON + PT_SFC_PI_K))) * sfc_ratio;
         const bool eng_off = eng_state == 0, eng_starting = eng_state == 1, eng_running = !(eng_off || eng_starting);
-        const double tau_shaft = eng_off ? out_frc * (0.01 * P_rated / w_rated) : (eng_starting ? tau_start : tau_run);
+        const double tau_shaft = eng_off ? out_frc * kc<KC_P_TAU_FRC>(K) : (eng_starting ? tau_start : tau_run);
         const double mdot = eng_running ? SFC_run * P_run : 0.0;
         const double tau_load = tau_p.x;  // gear_ratio * τ_prop
         DUO_MARK(1, 9);   // engine done
         emit.xwait(DUO_PT_X);   // ----- role D's point X: it has read the fuel row (and the wrench): the rows below may be rewritten in place -----
-        emit(FB_X_ENG_OMEGA, (tau_shaft + tau_load) / (J_eng + prop_Jxx));
+        emit(FB_X_ENG_OMEGA, kc_div<KC_P_INV_J>(tau_shaft + tau_load, K));
         // ----- fuel (c172.jl:607-616) -----
         (void)x_fuel;
-        emit(FB_X_FUEL, -mdot / (m_full - m_res));
+        emit(FB_X_FUEL, kc_div<KC_P_INV_M_FUEL>(-mdot, K));
         __builtin_amdgcn_s_setprio(0);
         DUO_MARK(1, 10);   // end of role P's evaluation
         return st;

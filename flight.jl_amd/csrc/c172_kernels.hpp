@@ -1178,6 +1178,25 @@ constexpr int DUO_NDL_WA = 13;
 constexpr int DUO_NDL_X = 14;
 template <int KIN, bool X> constexpr int duo_ndl() { return (KIN == FB_KIN_WA && !X) ? DUO_NDL_WA : (X ? DUO_NDL_X : DUO_ND); }
 static_assert(DUO_NDL_WA >= 1 && DUO_NDL_WA <= DUO_ND && DUO_NDL_X >= 1 && DUO_NDL_X <= DUO_ND, "");
+// How many of role P's fp64 constants stay RESIDENT in its registers for the whole launch (the first duo_nk() ids of the KC_* list,
+// c172_device_impl.inc "resident-capable constants" and c172_duo_device.hpp: a register pair each). The kernel is allocated what role D
+// needs — 248 registers in the WA Cessna172Sv0 instance — and role P touches ~122 of them: a constant in the idle ones costs nothing per
+// evaluation, rebuilt at the point of use it costs two moves. Per instance and by measurement: the WA Cessna172Sv0 instance keeps the
+// whole list (docs/design/k_step_duo.md "Round 7", profiles/r07_ab_resident_constants.txt); every other instance keeps none, and
+// its code is what it was, until an A/B of its own says otherwise.
+template <int KIN, bool X, bool PERENV> constexpr int duo_nk() { return (KIN == FB_KIN_WA && !X && !PERENV) ? (int)KC_COUNT : 0; }
+template <int NK>
+struct DuoK {
+    double r[NK];
+    template <int I> static constexpr bool resident() { return I < NK; }
+    template <int I> __device__ __forceinline__ double get() const { if constexpr (I < NK) return r[I]; else return KC<I>::v; }
+    // once per launch, under a full EXEC mask (ahead of every divergent branch of the role): each value made opaque, so that the
+    // compiler can neither fold it into its uses nor rebuild it there
+    template <int I = 0> __device__ __forceinline__ void init() {
+        if constexpr (I < NK) { double c = KC<I>::v; asm volatile("" : "+v"(c)); r[I] = c; init<I + 1>(); }
+    }
+};
+template <> struct DuoK<0> : KLit { __device__ __forceinline__ void init() {} };
 // Per-aircraft launch constants cost a role twenty registers each if they ride through the evaluation. Role D reads the payload's
 // ten mass-property sums from an LDS panel at the point of use and fetches its aerodynamic sums from global memory at the start of
 // the evaluation (one batch of loads, consumed after the table locations).
@@ -1520,6 +1539,8 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     };
     if (role == 1) {
         // ================= role P =================
+        DuoK<duo_nk<KIN, X, PERENV>()> kres;   // this role's resident constants (formed here: every lane of the wave is active)
+        kres.init();
         InputsDuoP in;
         in.throttle = 0; in.mixture = 0; in.ui = 0;
         [[maybe_unused]] double xa[X ? NAL : 1], ca[X ? NAL : 1];   // Cessna172Xv2: actuator positions x_n and the commands in force
@@ -1662,7 +1683,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     emit.xwait(DUO_PT_X);
                     (void)xv; (void)aux; (void)inl;
 #else
-                    rhs_duo<KIN, 1>(xv, 0, eng, inl, env_p, T, emit, aux);
+                    rhs_duo<KIN, 1>(xv, 0, eng, inl, env_p, T, emit, aux, kres);
 #endif
                     if constexpr (X) {
                         if (sk.last) {
