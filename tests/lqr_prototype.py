@@ -131,6 +131,6 @@ def scipy_batch(A, B, Q, R):
 
 
 def rel_dev(got, want):
-    """worst |got - want| / max|want| over the systems of a batch, each system scaled by its own largest entry"""
+    """(on purpose not support.state_scale: gains and Riccati solutions have no state rows) worst |got - want| / max|want| over the systems of a batch, each system scaled by its own largest entry"""
     axes = tuple(range(1, want.ndim))
     return float((np.abs(got - want).max(axis=axes) / np.abs(want).max(axis=axes)).max())

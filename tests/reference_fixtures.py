@@ -125,3 +125,67 @@ def compare_with_stored(lon, lat, y, tol, log=print):
     hold("γ", y[Y_GAMMA], 0.0); hold("climb_rate", -y[Y_VD], 0.0)
     log("max |ours − reference's stored trim| over the 28 design points: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
     return worst
+
+
+def design_trim_parameters_packed(n_copies=1):
+    """C172.TrimParameters(; Ob = Geographic(LatLon(), HEllip(h)), EAS, flaps) — c172x_design.jl:107-112; LatLon() is ϕ = λ = 0,
+    i.e. n_e = (1, 0, 0); everything else at its default (c172.jl:806-818)."""
+    EAS, h, flaps = (np.tile(a, n_copies) for a in design_nodes())
+    n = EAS.size
+    tp = np.zeros((18, n)); tp[0] = 1.0; tp[3] = h; tp[5] = EAS; tp[10] = 0.5; tp[11] = 0.5; tp[12] = flaps
+    tp[13:18] = np.array([75.0, 75.0, 0.0, 0.0, 50.0])[:, None]
+    return tp
+
+
+# ---- the printed linearisation of Robot2D.Vehicle and the design that follows from it (tests/test_reference_robot2d_linearization.py) ----
+R2_FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "robot2d_linearization.json")))
+A_REF, B_REF, C_REF, D_REF = (np.array(R2_FIX[k]) for k in "ABCD")
+R2_TOL = 1e-9
+
+
+def hold(name, got, want, log):
+    scale = np.abs(want).max()
+    err = np.abs(got - want).max() / scale
+    log(f"{name}: max |ours − reference| / max|reference| = {err:.2e}")
+    assert err <= R2_TOL, f"{name} deviates by {err:.3e}"
+    assert np.array_equal(got[want == 0.0] == 0.0, np.ones((want == 0.0).sum(), bool)) or np.abs(got[want == 0.0]).max() <= R2_TOL * scale
+    return err
+
+
+def check_jacobian_and_design(A, B, Cm, Dm, log):
+    for name, got, want in (("A", A, A_REF), ("B", B, B_REF), ("C", Cm, C_REF), ("D", Dm, D_REF)):
+        hold(name, got, want, log)
+    # cell 3: open-loop poles as printed (3 significant digits)
+    poles = np.sort(np.linalg.eigvals(A).real)
+    want = np.sort(np.array(R2_FIX["open_loop_poles_3_digits"]))
+    assert np.allclose(poles, want, rtol=5e-3, atol=1e-9), (poles, want)
+    # cell 6: the velocity-loop design on the reduced (η-free) model
+    import pytest
+    scipy_linalg = pytest.importorskip("scipy.linalg")
+    Ar, Br = A[:3, :3], B[:3]
+    Cz, Dz = Cm[1:2, :3], Dm[1:2]                               # z = v
+    A_aug = np.block([[Ar, np.zeros((3, 1))], [Cz, np.zeros((1, 1))]])
+    B_aug = np.vstack([Br, Dz])
+    q = R2_FIX["velocity_loop_design"]["Q_diag"]
+    Q = np.diag([q["ω"], q["v"], q["θ"], q["ξ_v"]]); R = np.array([[R2_FIX["velocity_loop_design"]["R_diag"]["m"]]])
+    P = scipy_linalg.solve_continuous_are(A_aug, B_aug, Q, R)
+    K_aug = np.linalg.solve(R, B_aug.T @ P)
+    M = np.linalg.inv(np.block([[Ar, Br], [Cz, Dz]]))
+    K_fbk, K_int = K_aug[:, :3], K_aug[:, 3:]
+    K_fwd = M[3:, 3:] + K_fbk @ M[:3, 3:]
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "flight.jl_amd", "flightbatch"))
+    import hdf5_min
+    assert_shipped_copy_is_the_references("flight.jl_amd/data/robot2d.h5")
+    g = hdf5_min.read_all(os.path.join(ROOT, "flight.jl_amd", "data", "robot2d.h5"))
+    for name, got in (("K_fbk", K_fbk), ("K_fwd", K_fwd), ("K_int", K_int)):
+        want = g[name].reshape(got.shape)
+        err = np.abs(got - want).max() / np.abs(want).max()
+        log(f"{name} redesigned from our Jacobian vs robot2d.h5: {err:.2e}")
+        assert err <= 1e-10, (name, got, want)
+    # cell 7: closed-loop poles of P_v as printed (the plant's η integrator stays at 0)
+    Acl = A_aug - B_aug @ K_aug
+    poles = np.sort(np.concatenate([[0.0], np.linalg.eigvals(Acl).real]))
+    want = np.sort(np.array(R2_FIX["velocity_loop_design"]["closed_loop_poles_3_digits"]))
+    assert np.allclose(poles, want, rtol=5e-3, atol=1e-9), (poles, want)
+    assert np.abs(np.linalg.eigvals(Acl).imag).max() < 1e-6        # dampreport prints damping ratio 1 for all of them

@@ -9,21 +9,10 @@ import pytest
 import conditioning
 
 from oracle_binding import OracleX
-from test_gpu_parity import lattice_trim_params, state_scale
+from support import H_E_ROW, abi_to_oracle_rows, geoid, h_e_row_abi, lattice_trim_params, seg_end, state_scale
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def ref_to_dev_rows(K):
-    """row k of the C ABI state (reference order) -> row of the oracle / device order (27 Sv0 rows, then the actuators)"""
-    return np.array([k if k < K["FB_X2_ACT"] else (27 + k - K["FB_X2_ACT"] if k < K["FB_X2_KIN"] else k - K["FB_NACT"]) for k in range(34)])
-
-
-def x_scale(x):
-    sc = np.ones_like(x)
-    sc[:27] = state_scale(x[:27])
-    return sc
 
 
 @pytest.fixture(scope="module")
@@ -48,11 +37,11 @@ def test_x2_init_matches_oracle(fb, oracle, gains):
     K = fb.K
     n = 1024
     w, sim, X, env, o = make_pair(fb, oracle, gains, n, seed=21)
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     ok = w.trim_success & o["ok"]
     assert (w.trim_success == o["ok"]).all() and ok.mean() > 0.6
     xo = o["x"][perm]                             # oracle rows re-ordered to the reference order (w.x is in that order)
-    assert np.max(np.abs(w.x - xo)[:, ok] / x_scale(o["x"])[perm][:, ok]) < 1e-7
+    assert np.max(np.abs(w.x - xo)[:, ok] / state_scale(o["x"])[perm][:, ok]) < 1e-7
     # actuator states = commands = trim values; control-law inputs aligned with the vehicle; both channels in direct
     assert np.array_equal(w.x[K["FB_X2_ACT"] + K["FB_ACT_THROTTLE"]], w.ctl.y("THROTTLE_CMD"))
     assert np.max(np.abs(w.cu - o["cu"])[:, ok]) < 1e-6 and np.max(np.abs(w.cs - o["cs"])[:, ok]) < 1e-6
@@ -90,7 +79,7 @@ def test_x2_closed_loop_trajectory_matches_oracle(fb, oracle, gains, same_grid, 
     w.cu = cu
     o["cu"] = np.ascontiguousarray(o["cu"]); o["cu"][:] = cu
     # start both from the GPU's initial condition so that only the stepping is compared
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     o["x"][perm] = w.x; o["cs"] = w.cs; o["u"] = w.u; o["ui"] = w.ui; o["s"] = w.s
     fb.step(sim, 10.0); w.sync()
     X.step(o, env, 0.01, 2, 1000)
@@ -99,7 +88,7 @@ def test_x2_closed_loop_trajectory_matches_oracle(fb, oracle, gains, same_grid, 
     ok = (st == 0)
     assert ok.mean() > 0.9
     xo = o["x"][perm]
-    sc = x_scale(o["x"])[perm]
+    sc = state_scale(o["x"])[perm]
     err = (np.abs(w.x - xo) / sc)[:, ok]
     print("X2 closed loop, max scaled state error after 1000 steps:", err.max(), "terminated:", int((~ok).sum()))
     assert err.max() < 1e-6
@@ -194,11 +183,10 @@ def test_x2_segment_guidance_matches_oracle(fb, oracle, gains):
     """Segment guidance (c172x_gdc.jl:232-329) in the loop: every aircraft gets its own target segment (left / right of its
     course, above / below), horizontal and vertical guidance requested; 30 s against the oracle, then the same run continued
     to 120 s must have captured the segment."""
-    from test_oracle_c172x import seg_end
     K = fb.K
     n = 512
     w, sim, X, env, o = make_pair(fb, oracle, gains, n, seed=23)
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     fb.f_ode(w)
     y = w.y
     rng = np.random.default_rng(11)
@@ -215,7 +203,7 @@ def test_x2_segment_guidance_matches_oracle(fb, oracle, gains):
     X.step(o, env, 0.01, 2, 3000)
     ok = (w.status == 0) & (o["status"] == 0) & w.trim_success
     assert ok.mean() > 0.6 and np.array_equal(w.status != 0, o["status"] != 0)
-    err = (np.abs(w.x - o["x"][perm]) / x_scale(o["x"])[perm])[:, ok]
+    err = (np.abs(w.x - o["x"][perm]) / state_scale(o["x"])[perm])[:, ok]
     cerr = (np.abs(w.cs - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0))[:, ok]
     uerr = (np.abs(w.cu - o["cu"]) / np.maximum(np.abs(o["cu"]), 1.0))[:, ok]
     print("guidance closed loop after 3000 steps: state", err.max(), "record", cerr.max(), "inputs", uerr.max())
@@ -301,7 +289,7 @@ def test_x2_control_laws_fuzz(fb, oracle, gains, variant, kin, monkeypatch):
     for k in ("THROTTLE_CMD",):
         cs[K["FB_CS_" + k]] = rng.uniform(0, 1, n)
     w.cu = cu; w.cs = cs
-    perm = abi_to_dev_rows(K, kin)
+    perm = abi_to_oracle_rows(K, "x2", kin)
     X = OracleX(oracle, gains)
     st = dict(x=np.zeros((34, n)), u=w.u, ui=w.ui, s=w.s, cu=cu.copy(), cs=cs.copy())
     st["x"][perm] = w.x
@@ -320,13 +308,6 @@ def test_x2_control_laws_fuzz(fb, oracle, gains, variant, kin, monkeypatch):
     w.close()
 
 
-def abi_to_dev_rows(K, kin):
-    """row k of the C ABI state of Cessna172Xv2(kinematics) -> row of the oracle / device order, in which every mechanisation keeps the
-    nine kinematic rows 12..20 and leaves the ones it does not use at zero (ECEF: row 20; NED: rows 18-20)"""
-    unused = {"WA": (), "ECEF": (20,), "NED": (18, 19, 20)}[kin]
-    return np.array([r for r in ref_to_dev_rows(K) if r not in unused])
-
-
 @pytest.mark.parametrize("kin", ["WA", "ECEF", "NED"])
 def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
     """Cessna172Xv2(ECEF()) / Cessna172Xv2(NED()) (FA/c172/c172x/c172x2.jl:57-59 over FP/kinematics.jl:250-425) against the oracle
@@ -335,7 +316,7 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
     hard landings that end in GroundCrash and softer ones that roll out, status word, step and place of every termination included;
     the descent is run twice and must repeat bit for bit (what a spill-placement fault of the compiler would break: docs/design/k_step_air.md)."""
     K = fb.K
-    perm = abi_to_dev_rows(K, kin)
+    perm = abi_to_oracle_rows(K, "x2", kin)
     nx = 34 - {"WA": 0, "ECEF": 1, "NED": 3}[kin]
     oracle.lib.fo_set_kinematics(K["FB_KIN_" + kin])
     try:
@@ -353,7 +334,7 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
         assert w.x.shape[0] == nx and perm.size == nx and (w.trim_success == o["ok"]).all() and ok.mean() > 0.6
         unused = np.setdiff1d(np.arange(34), perm)
         assert (o["x"][unused] == 0).all()
-        sc = x_scale(o["x"])[perm]
+        sc = state_scale(o["x"])[perm]
         assert np.max(np.abs(w.x - o["x"][perm])[:, ok] / sc[:, ok]) < 1e-7
         assert np.max(np.abs(w.cu - o["cu"])[:, ok]) < 1e-6 and np.max(np.abs(w.cs - o["cs"])[:, ok]) < 1e-6
         xd = np.zeros((nx, n)); fb.f_ode(w, xd)
@@ -381,13 +362,12 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
         assert np.array_equal(st, sto)
         fine = st == 0
         assert fine.mean() > 0.9
-        err = (np.abs(w.x - o["x"][perm]) / x_scale(o["x"])[perm])[:, fine]
+        err = (np.abs(w.x - o["x"][perm]) / state_scale(o["x"])[perm])[:, fine]
         cerr = (np.abs(w.cs - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0))[:, fine]
         print(f"Xv2({kin}) closed loop after 1000 steps: max scaled state error {err.max():.2e}, control-law record {cerr.max():.2e}")
         assert err.max() < 1e-6 and cerr.max() < 1e-6 and np.array_equal(w.s[:, fine], o["s"][:, fine])
         w.close()
         # ---- the ground-capable instance: autopilot descents onto the runway
-        from test_gpu_termination import geoid
         n = 2048
         rng = np.random.default_rng(61)
         N0 = geoid(oracle, np.zeros(1), np.zeros(1))[0]
@@ -416,7 +396,7 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
         o_start = {k: np.array(v, copy=True) for k, v in o.items() if isinstance(v, np.ndarray)}
         X.step_term(o, env, 0.01, 2, 1200)
         # the oracle against itself (tests/conditioning.py): v_eb_b nudged once per aircraft as it comes within wheel reach of the runway
-        h_row_o = {"WA": 20, "ECEF": 19, "NED": 17}[kin]
+        h_row_o = H_E_ROW[kin]
         pert_ulp = conditioning.x2_perturbed_runs(X, o_start, env, 1200, h_row_o, N0, None, K=2, seed=1, threads=16)
         pert_rel = conditioning.x2_perturbed_runs(X, o_start, env, 1200, h_row_o, N0, 1e-12, K=4, jitter=conditioning.ULP_R, seed=2, threads=16)
     finally:
@@ -428,8 +408,8 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
     tstep, twhere = a["term"]
     assert np.array_equal(twhere, o["term_where"]) and np.array_equal(tstep, o["term_step"])
     xo = o["x"][perm]
-    err = np.abs(a["x"] - xo) / x_scale(o["x"])[perm]
-    he_row = int(np.where(perm == {"WA": 20, "ECEF": 19, "NED": 17}[kin])[0][0])
+    err = np.abs(a["x"] - xo) / state_scale(o["x"])[perm]
+    he_row = h_e_row_abi(K, "x2", kin)
     flying = ~term & (xo[he_row] - N0 > 8.0)
     rolling = ~term & ~flying
     print(f"Xv2({kin}): max scaled state error, crashed {err[:, term].max():.2e} | still flying {err[:, flying].max() if flying.any() else 0.0:.2e} "
@@ -447,7 +427,7 @@ def test_x2_ecef_and_ned_mechanisations(fb, oracle, gains, kin):
     assert cerr[:, term | flying].max() < 1e-6
 
     def lane_err(xx, cc):   # per-aircraft max scaled distance from the nominal oracle run, state rows (oracle order) and control-law record
-        return np.maximum((np.abs(xx - o["x"]) / x_scale(o["x"])).max(0), (np.abs(cc - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0))
+        return np.maximum((np.abs(xx - o["x"]) / state_scale(o["x"])).max(0), (np.abs(cc - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0))
     assert rolling.sum() >= 100
     per_lane = np.maximum(err.max(0), cerr.max(0))[rolling]
     E_ulp = np.stack([lane_err(p["x"], p["cs"])[rolling] for p in pert_ulp])

@@ -33,7 +33,6 @@ within 4 m of their terrain) are counted on the oracle alone, and asserted: a re
 Tolerances are those of the nearest instance already covered (tests/test_gpu_env.py, test_gpu_parity.py, test_gpu_f32.py).
 """
 import contextlib
-import hashlib
 import os
 import sys
 
@@ -41,11 +40,7 @@ import numpy as np
 import pytest
 
 from oracle_binding import OracleX
-from test_gpu_parity import state_scale
-from test_gpu_c172x import abi_to_dev_rows
-from test_gpu_duo import stepper
-from test_gpu_env import random_env
-from test_gpu_termination import geoid
+from support import H_E_ROW, N_KIN, abi_to_oracle_rows, digest_dict, geoid, random_env, state_scale, stepper
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import F32_TOLERANCE   # noqa: E402
@@ -61,24 +56,7 @@ NEAR = 4.0                       # weight on wheels is looked for below this cle
 H_TRN = 120.0                    # the batch-wide block's terrain elevation
 TOL = 1e-6                       # airborne lanes: scaled state / control-law record (test_gpu_env.py, test_gpu_parity.py)
 TOL_GROUND = 1e-3                # lanes in ground contact: altitude and attitude (test_per_aircraft_terrain_elevation_ground_contact)
-NK = {"WA": 9, "ECEF": 8, "NED": 6}
-H_ROW = {"WA": 20, "ECEF": 19, "NED": 17}        # h_e in the oracle's 27-row layout
 ATT = {"WA": slice(12, 16), "ECEF": slice(12, 16), "NED": slice(12, 15)}   # q_wb / q_eb / (ψ, θ, φ)
-
-
-def oracle_rows(K, x2, kin):
-    """row k of the C ABI state -> row of the oracle's layout (27 Cessna172Sv0 rows with the unused kinematic rows zero, then the actuators)"""
-    if x2:
-        return abi_to_dev_rows(K, kin)
-    return np.array(list(range(12 + NK[kin])) + list(range(21, 27)))
-
-
-def scale(xo, kin):
-    """state_scale with the WA layout's meaning in every mechanisation: attitude / position rows 1, the altitude max(|h_e|, 1)"""
-    sc = np.ones_like(xo)
-    sc[:27] = state_scale(xo[:27])
-    sc[H_ROW[kin]] = np.maximum(np.abs(xo[H_ROW[kin]]), 1.0)
-    return sc
 
 
 _SCENARIO = {}
@@ -103,7 +81,7 @@ def scenario(fb, oracle, x2, rows):
     h_own = U(20.0, 400.0)
     h_trn = h_own if rows else np.full(N, H_TRN)
     N0 = geoid(oracle, lat, lon)
-    # group 1: the lattice of test_gpu_parity.lattice_trim_params, over the aircraft's own terrain
+    # group 1: the lattice of support.lattice_trim_params, over the aircraft's own terrain
     clr1 = U(200.0, 3000.0)          # clearance over the terrain, m
     eas1 = U(35.0, 55.0)
     gam1 = U(-0.02, 0.02)            # flight-path angle, rad
@@ -158,7 +136,7 @@ def scenario(fb, oracle, x2, rows):
 
     def perturb(x, kin):
         """the start state in C ABI order: groups 1 and 2 off trim in rates and velocity, the aircraft on their wheels set down and slowed to a roll"""
-        d0 = (K["FB_X2_KIN"] if x2 else 12) + NK[kin]
+        d0 = (K["FB_X2_KIN"] if x2 else 12) + N_KIN[kin]
         x = x.copy()
         x[d0:d0 + 3] += dw
         x[d0 + 3:d0 + 6] += dv
@@ -196,13 +174,6 @@ def mechanisation(fb, oracle, kin, rows):
             oracle.lib.fo_set_kinematics(fb.K["FB_KIN_WA"])
 
 
-def _digest(d):
-    h = hashlib.sha256()
-    for k in sorted(d):
-        h.update(k.encode()); h.update(np.ascontiguousarray(d[k]).tobytes())
-    return h.hexdigest()
-
-
 _TRIM_OK = {}
 
 
@@ -231,12 +202,12 @@ def oracle_run(fb, oracle, x2, kin, env, start, h_trn, N0):
     and the first step with weight on wheels (-1: never)"""
     K = fb.K
     rows = env.ndim == 2
-    key = (x2, kin, _digest(start), _digest(dict(env=env, h=h_trn)))
+    key = (x2, kin, digest_dict(start), digest_dict(dict(env=env, h=h_trn)))
     if key in _ORACLE:
         return _ORACLE[key]
-    rmap = oracle_rows(K, x2, kin)
+    rmap = abi_to_oracle_rows(K, "x2" if x2 else "s0", kin)
     x = np.zeros((34 if x2 else 27, N)); x[rmap] = start["x"]
-    hrow, ldg = H_ROW[kin], K["FB_Y_LDG"]
+    hrow, ldg = H_E_ROW[kin], K["FB_Y_LDG"]
     X = OracleX(oracle, fb.ctl_gains.ctl_gains_blob()) if x2 else None
     o = dict(x=x, u=start["u"].copy(), ui=start["ui"].copy(), s=start["s"].copy(), status=np.zeros(N, np.int32), nstep=0,
              term_step=np.full(N, -1, np.int64), term_where=np.zeros(N, np.int32))
@@ -320,7 +291,7 @@ def device_run(fb, oracle, x2, kin, rows, duo, spl, dtype="f64"):
         fb.f_init(w, sc["tp"])
     ok = w.trim_success
     # the C ABI presents the mechanisation's own rows (fb_dims)
-    nx = 18 + NK[kin] + (K["FB_NACT"] if x2 else 0)
+    nx = 18 + N_KIN[kin] + (K["FB_NACT"] if x2 else 0)
     assert w.nx == nx and w.x.shape == (nx, N)
     w.set_state(sc["perturb"](w.x, kin), w.s)
     if x2:
@@ -360,7 +331,7 @@ def rows_matter(fb, oracle, x2, kin, start, sc, o, ok, label):
     flat = oracle_run(fb, oracle, x2, kin, oracle.default_env(), start, np.zeros(N), sc["N0"])
     live = ok & (o["status"] == 0)
     air = live & (o["first_wow"] < 0) & (flat["status"] == 0)
-    d = (np.abs(flat["x"] - o["x"]) / scale(o["x"], kin)).max(0)
+    d = (np.abs(flat["x"] - o["x"]) / state_scale(o["x"], kin)).max(0)
     touched = ok & (o["first_wow"] >= 0)
     print(f"{label}: without the rows: airborne lanes differ by {d[air].min():.2e} .. {d[air].max():.2e}; of {int(touched.sum())} that touch down, "
           f"{int((flat['first_wow'][touched] < 0).sum())} never do and {int((flat['first_wow'] == o['first_wow'])[touched].sum())} do so at the same step")
@@ -372,16 +343,16 @@ def compare(fb, x2, kin, dev, o, wow, ok, label):
     """status words and termination record on every aircraft; discrete states on the live ones; airborne lanes at the strict
     tolerance, lanes that had weight on wheels in altitude and attitude"""
     K = fb.K
-    rmap = oracle_rows(K, x2, kin)
+    rmap = abi_to_oracle_rows(K, "x2" if x2 else "s0", kin)
     assert np.array_equal(dev["status"], o["status"]), f"{label}: {int((dev['status'] != o['status']).sum())} status words differ"
     assert np.array_equal(dev["tstep"], o["term_step"]) and np.array_equal(dev["twhere"], o["term_where"]), f"{label}: termination record"
     live = o["status"] == 0
     assert np.array_equal(dev["s"][:, live], o["s"][:, live]), f"{label}: discrete states differ"
     xo = o["x"][rmap]
-    err = (np.abs(dev["x"] - xo) / scale(o["x"], kin)[rmap]).max(0)
+    err = (np.abs(dev["x"] - xo) / state_scale(o["x"], kin)[rmap]).max(0)
     cerr = (np.abs(dev["cs"] - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0) if x2 else np.zeros(N)
     strict, ground = ok & live & ~wow, ok & live & wow
-    hr = int(np.nonzero(rmap == H_ROW[kin])[0][0])
+    hr = int(np.nonzero(rmap == H_E_ROW[kin])[0][0])
     att = [int(np.nonzero(rmap == r)[0][0]) for r in range(ATT[kin].start, ATT[kin].stop)]
     dh, dq = np.abs(dev["x"][hr] - xo[hr]), np.abs(dev["x"][att] - xo[att]).max(0)
     print(f"{label}: worst scaled error on {int(strict.sum())} airborne lanes: state {err[strict].max():.2e}, control-law record {cerr[strict].max():.2e}; "
@@ -435,7 +406,7 @@ def test_f32_handle_without_rows_runs_the_fp32_stepper(fb, oracle):
     # launch length); two fp64 steppers differ by accumulated fp64 rounding, orders below 1e-10
     f64 = device_run(fb, oracle, False, "WA", False, True, 50)
     assert np.array_equal(f64["start"]["x"], dev["start"]["x"])
-    apart = (np.abs(dev["x"] - f64["x"]) / scale(f64["x"], "WA")).max(0)[g1]
+    apart = (np.abs(dev["x"] - f64["x"]) / state_scale(f64["x"], "WA")).max(0)[g1]
     print(f"{label}: group 1 against the fp64 handle: scaled distance {apart.min():.1e} .. {apart.max():.1e}")
     assert apart.min() > 1e-10, "an FB_F32 handle without rows was stepped in fp64"
     near = (g[2] | g[3]) & ok

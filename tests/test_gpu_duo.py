@@ -2,30 +2,12 @@
 waves per SIMD, the default) and the one-wave-per-SIMD k_step_air (FLIGHTBATCH_DUO=0). Same physics, different evaluation order and fma
 contraction: they agree to rounding, lane by lane, including on the lanes that are not ordinary — beyond the end of a ragged batch,
 terminated before the launch, sitting on the ground, sinking through the hand-over clearance in the middle of a launch."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from support import abi_to_oracle_rows, flying_batch, geoid, h_e_row_abi, stepper
+
 pytestmark = pytest.mark.gpu
-
-
-H_E_ROW = {"WA": 20, "ECEF": 19, "NED": 17}     # the ellipsoidal altitude in the C ABI's state of each mechanisation
-
-
-@contextlib.contextmanager
-def stepper(duo):
-    """worlds created inside are stepped by k_step_duo (duo) or by the one-wave k_step_air (FLIGHTBATCH_DUO=0, read when a handle is created)"""
-    old = os.environ.get("FLIGHTBATCH_DUO")
-    os.environ["FLIGHTBATCH_DUO"] = "1" if duo else "0"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["FLIGHTBATCH_DUO"]
-        else:
-            os.environ["FLIGHTBATCH_DUO"] = old
 
 
 def _world(fb, n, duo, kin="WA"):
@@ -33,14 +15,14 @@ def _world(fb, n, duo, kin="WA"):
         return fb.BatchedWorld(n, kinematics=kin)
 
 
-def _scale(x):
+def _scale(x):   # (on purpose not support.state_scale: plain max(|x|, 1e-3) on every row is the stricter scale between two device steppers)
     return np.maximum(np.abs(x), 1e-3)
 
 
 @pytest.mark.parametrize("n,spl,kin", [(1000, 50, "WA"), (333, 7, "WA"), (64, 1, "WA"), (1000, 50, "ECEF"), (333, 7, "NED"), (1000, 50, "NED"), (64, 1, "ECEF")])
 def test_duo_and_air_steppers_agree(fb, n, spl, kin):
     rng = np.random.default_rng(23 + n)
-    he = H_E_ROW[kin]
+    he = h_e_row_abi(fb.K, "s0", kin)
     h_trn = 250.0
     cruise = rng.random(n) < 0.6
     h = np.where(cruise, h_trn + rng.uniform(300, 4000, n), h_trn + rng.uniform(11, 30, n))       # the rest: short final, will cross 10 m
@@ -98,7 +80,6 @@ def test_wave_pairs_leaving_at_different_steps(fb, oracle):
     s_barrier counting only the waves that have not ended. Here every pair of two workgroups runs dry at a DIFFERENT step of one launch
     (its 64 aircraft zoom through the ISA ceiling, pair by pair; the last pair of each workgroup flies on), with a few lanes terminated
     before the launch mixed in: the survivors must agree with the one-wave stepper, the terminated ones with the oracle."""
-    from test_gpu_termination import flying_batch, geoid
     n = 512
     rng = np.random.default_rng(77)
     lat = rng.uniform(-1.0, 1.0, n); lon = rng.uniform(-3.0, 3.0, n)
@@ -153,13 +134,8 @@ def test_x2_duo_and_air_steppers_agree(fb, n, spl, kin):
     st0 = np.zeros(n, np.int32); st0[rng.random(n) < 0.05] = K["FB_ST_NAN"]
     out = {}
     for duo in (False, True):
-        old = os.environ.get("FLIGHTBATCH_DUO")
-        os.environ["FLIGHTBATCH_DUO"] = "1" if duo else "0"
-        try:
+        with stepper(duo):
             w = fb.Cessna172Xv2World(n, gains=gains, kinematics=kin)
-        finally:
-            if old is None: del os.environ["FLIGHTBATCH_DUO"]
-            else: os.environ["FLIGHTBATCH_DUO"] = old
         w.set_params(h_terrain=h_trn, wind_ned=(2.0, -1.0, 0.0))
         sim = fb.Simulation(w, dt=0.01, Δt=0.02, save_on=False, steps_per_launch=spl)
         fb.init(sim, tp)
@@ -182,10 +158,8 @@ def test_x2_duo_and_air_steppers_agree(fb, n, spl, kin):
     assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["s"], b["s"])
     live = a["ok"] & (a["status"] == 0)
     # C ABI row (reference order: the actuators behind the power plant, the mechanisation's unused rows dropped) of the device's altitude row
-    perm = [k if k < K["FB_X2_ACT"] else (27 + k - K["FB_X2_ACT"] if k < K["FB_X2_KIN"] else k - K["FB_NACT"]) for k in range(34)]
-    perm = [r for r in perm if r not in {"WA": (), "ECEF": (20,), "NED": (18, 19, 20)}[kin]]
-    perm_he = perm.index({"WA": 20, "ECEF": 19, "NED": 17}[kin])
-    assert a["x"].shape[0] == len(perm)
+    perm_he = h_e_row_abi(K, "x2", kin)
+    assert a["x"].shape[0] == len(abi_to_oracle_rows(K, "x2", kin))
     landed = live & (a["x"][perm_he] - h_trn < 8.0)
     flying = live & ~landed
     assert flying.sum() > 0.4 * n and (~cruise & live).sum() > 0.1 * n

@@ -5,19 +5,9 @@ verb (trim, f_ode!, f_step!, the steppers of both passes, Cessna172Xv2's control
 import numpy as np
 import pytest
 
-from test_gpu_parity import lattice_trim_params, state_scale
+from support import N_KIN, abi_to_oracle_rows, lattice_trim_params, random_env, state_scale
 
 pytestmark = pytest.mark.gpu
-
-
-def random_env(fb, n, seed, h_trn=None):
-    K = fb.K
-    rng = np.random.default_rng(seed)
-    e = np.zeros((K["FB_NENV"], n))
-    e[K["FB_ENV_WIND_N"]] = rng.uniform(-12, 12, n); e[K["FB_ENV_WIND_E"]] = rng.uniform(-12, 12, n); e[K["FB_ENV_WIND_D"]] = rng.uniform(-2, 2, n)
-    e[K["FB_ENV_T_SL"]] = rng.uniform(258.0, 313.0, n); e[K["FB_ENV_P_SL"]] = rng.uniform(97000.0, 104500.0, n)
-    e[K["FB_ENV_H_TERRAIN"]] = rng.uniform(-50.0, 150.0, n) if h_trn is None else h_trn
-    return e
 
 
 @pytest.mark.parametrize("kin", ["WA", "ECEF", "NED"])
@@ -27,7 +17,7 @@ def test_per_aircraft_env_trim_f_ode_and_trajectory_match_oracle(fb, oracle, kin
     batch-wide default environment ends elsewhere)."""
     K = fb.K
     n = 4096
-    nk = {"WA": 9, "ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     tp = lattice_trim_params(fb, n, seed=61)
     env6 = random_env(fb, n, 7)
     w = fb.BatchedWorld(n, kinematics=kin)
@@ -109,7 +99,6 @@ def test_uniform_rows_equal_the_batch_wide_block(fb):
 def test_per_aircraft_env_xv2_closed_loop_matches_oracle(fb, oracle):
     """Cessna172Xv2 with the autopilot every 2 steps, each aircraft in its own wind and air mass, 500 closed-loop steps vs the oracle"""
     from oracle_binding import OracleX
-    from test_gpu_c172x import ref_to_dev_rows, x_scale
     K = fb.K
     n = 1024
     gains = fb.ctl_gains.ctl_gains_blob()
@@ -127,7 +116,7 @@ def test_per_aircraft_env_xv2_closed_loop_matches_oracle(fb, oracle):
     cu[K["FB_CU_EAS_REF"]] += rng.uniform(-3, 3, n); cu[K["FB_CU_CLM_REF"]] += rng.uniform(-1.5, 1.5, n)
     cu[K["FB_CU_PHI_REF"]] += rng.uniform(-0.3, 0.3, n); cu[K["FB_CU_CHI_REF"]] += rng.uniform(-0.5, 0.5, n)
     w.cu = cu
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     X = OracleX(oracle, gains)
     oenv = oracle.env_rows(env6)
     o = dict(x=np.empty((34, n)), u=w.u, ui=w.ui, s=w.s, cu=np.ascontiguousarray(cu), cs=w.cs, status=np.zeros(n, np.int32), nstep=0)
@@ -137,7 +126,7 @@ def test_per_aircraft_env_xv2_closed_loop_matches_oracle(fb, oracle):
         X.step(o, oenv, 0.01, 2, 500)
     assert np.array_equal(w.status, o["status"])
     live = (o["status"] == 0) & ok
-    err = (np.abs(w.x - o["x"][perm]) / x_scale(o["x"])[perm])[:, live]
+    err = (np.abs(w.x - o["x"][perm]) / state_scale(o["x"])[perm])[:, live]
     cerr = (np.abs(w.cs - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0))[:, live]
     print("Xv2, per-aircraft environment: max scaled error after 500 closed-loop steps %.3e (record %.3e)" % (err.max(), cerr.max()))
     assert err.max() < 1e-6 and cerr.max() < 1e-6

@@ -6,7 +6,7 @@ import pytest
 import os
 import sys
 
-from test_gpu_parity import lattice_trim_params, state_scale
+from support import lattice_trim_params, state_scale
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import F32_TOLERANCE   # noqa: E402

@@ -7,7 +7,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import state_scale
+from support import DEFAULT_VP, N_KIN, abi_to_oracle_rows, gains_from_h5, robot2d_oracle_init as oracle_init, robot2d_oracle_run as run, state_scale
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,7 +84,6 @@ def test_config3_per_gpu_share_xv2_autopilot(fb, oracle):
     sample against the CPU oracle at 1e-6, and big batch == small batch bit for bit."""
     import bench
     from oracle_binding import OracleX
-    from test_gpu_c172x import ref_to_dev_rows, x_scale
     K = fb.K
     n = bench.N_TOTAL // 2
     EAS, h, psi, cell = bench.lattice(3, n)
@@ -103,7 +102,7 @@ def test_config3_per_gpu_share_xv2_autopilot(fb, oracle):
         fb.step(sim, 0.5)
     w.sync()
     x1, s1, st, cs1 = w.x, w.s, w.status, w.cs
-    perm = ref_to_dev_rows(K)                     # C ABI row -> oracle / device row
+    perm = abi_to_oracle_rows(K, "x2")                     # C ABI row -> oracle / device row
     row = {k: int(np.where(perm == k)[0][0]) for k in (8, 12, 16, 20)}
     # ---- invariants on ALL 524 288 aircraft
     assert (st == 0).all(), f"{(st != 0).sum()} aircraft terminated"
@@ -126,7 +125,7 @@ def test_config3_per_gpu_share_xv2_autopilot(fb, oracle):
     o["x"][perm] = x0[:, sel]
     X.step(o, env, 0.01, 2, 1000, threads=min(oracle.max_threads(), bench.usable_cores()))
     assert (o["status"] == 0).all() and np.array_equal(o["s"], s1[:, sel])
-    err = np.abs(x1[:, sel] - o["x"][perm]) / x_scale(o["x"])[perm]
+    err = np.abs(x1[:, sel] - o["x"][perm]) / state_scale(o["x"])[perm]
     cerr = np.abs(cs1[:, sel] - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)
     print("configs[3] at N = 524 288 per GPU: max scaled error of 512 stratified aircraft after 1000 closed-loop steps: %.3e (control-law record %.3e)" % (err.max(), cerr.max()))
     assert err.max() < 1e-6 and cerr.max() < 1e-6
@@ -212,7 +211,7 @@ def test_config2_full_size_other_mechanisations(fb, oracle, kin):
     import bench
     K = fb.K
     n = bench.N_TOTAL
-    nk = {"ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     EAS, h, psi, cell = bench.lattice(0)
     w = fb.BatchedWorld(n, kinematics=kin)
     fb.f_init(w, fb.TrimParameters(EAS=EAS, h_e=h, ψ_nb=psi))
@@ -260,8 +259,6 @@ def test_config4_mixed_fp32_fleet_as_stated(fb, oracle):
     bench.py's extra.fleet leg reports as its tolerance)."""
     import ctypes as C
     import bench
-    from test_oracle_robot2d import DEFAULT_VP, gains_from_h5, run
-    from test_gpu_robot2d import oracle_init
     tol = bench.F32_TOLERANCE
     n = bench.N_TOTAL
     KC, KR = fb.K["FB_MODEL_C172S0"], fb.K["FB_MODEL_ROBOT2D"]

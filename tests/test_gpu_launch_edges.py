@@ -25,15 +25,12 @@ Not covered, on purpose: a hand-over first detected at the evaluation at x_{n+1}
 `if (run)` in k_step_air decide a one-step launch). A natural trajectory does not get there: the k4 point and x_{n+1} agree in height
 to high order, so a lane that enters the band is handed over at k4 or earlier. Only a contrived state would reach it.
 """
-import hashlib
 
 import numpy as np
 import pytest
 
 from oracle_binding import OracleX
-from test_gpu_c172x import ref_to_dev_rows, x_scale
-from test_gpu_duo import stepper
-from test_gpu_termination import geoid
+from support import abi_to_oracle_rows, digest, geoid, state_scale, stepper
 
 pytestmark = pytest.mark.gpu
 
@@ -83,13 +80,6 @@ _ORACLE = {}   # (ratio, digest of the start state) -> oracle run with its cover
 _DEVICE = {}   # (spl, duo, ratio) -> device result
 
 
-def _digest(*arrays):
-    h = hashlib.sha256()
-    for a in arrays:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
-
-
 def device_run(fb, oracle, spl, duo, ratio):
     key = (spl, duo, ratio)
     if key in _DEVICE:
@@ -124,11 +114,11 @@ def oracle_run(fb, oracle, ratio, dev):
     """the oracle from the device's start state, one step at a time, with the same writes at the same steps; the per-step clearance
     of every aircraft is kept to count the band crossings"""
     st = dev["start"]
-    key = (ratio, _digest(*(st[k] for k in ("x", "cs", "cu", "u", "ui", "s"))))
+    key = (ratio, digest(*(st[k] for k in ("x", "cs", "cu", "u", "ui", "s"))))
     if key in _ORACLE:
         return _ORACLE[key]
     K = fb.K
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     X = OracleX(oracle, fb.ctl_gains.ctl_gains_blob())
     env = oracle.default_env(h_trn=H_TRN)
     o = X.trim_init(dev["tp"].pack(N), fb.TrimState(N), env, 0.01 * ratio, threads=16)
@@ -170,12 +160,12 @@ def test_x2_through_the_handover_band(fb, oracle, spl, duo, ratio):
     dev = device_run(fb, oracle, spl, duo, ratio)
     o, cov = oracle_run(fb, oracle, ratio, dev)
     check_coverage(cov, dev["groups"], label)
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     thrown = int((o["status"] != 0).sum())
     print(f"{label}: threw {thrown} (oracle), {int((dev['status'] != 0).sum())} (device)")
     assert np.array_equal(dev["status"], o["status"]), f"{label}: {int((dev['status'] != o['status']).sum())} status words differ"
     assert np.array_equal(dev["tstep"], o["term_step"]) and np.array_equal(dev["twhere"], o["term_where"])
-    err = np.abs(dev["x"] - o["x"][perm]) / x_scale(o["x"])[perm]
+    err = np.abs(dev["x"] - o["x"][perm]) / state_scale(o["x"])[perm]
     cerr = np.abs(dev["cs"] - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)
     per = err.max(0)
     print(f"{label}: max scaled error, state {err.max():.2e} (group a {per[dev['groups']['a']].max():.2e}, b {per[dev['groups']['b']].max():.2e}, "
@@ -187,7 +177,7 @@ def test_x2_through_the_handover_band(fb, oracle, spl, duo, ratio):
     if not duo:
         # the two airborne steppers at the same launch length: the same trajectories to rounding
         ref = device_run(fb, oracle, spl, True, ratio)
-        d = (np.abs(dev["x"] - ref["x"]) / x_scale(o["x"])[perm]).max()
+        d = (np.abs(dev["x"] - ref["x"]) / state_scale(o["x"])[perm]).max()
         dc = (np.abs(dev["cs"] - ref["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max()
         print(f"{label}: one-wave against duo: state {d:.2e}, record {dc:.2e}")
         assert np.array_equal(dev["status"], ref["status"]) and np.array_equal(dev["s"], ref["s"])

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import reference_fixtures as rf
+from support import clock as _clock
 
 pytestmark = pytest.mark.gpu
 W_RATED = 2700 * np.pi / 30
@@ -25,7 +26,7 @@ def _mats(lss, order=(1, 2, 0)):
 
 # ---- 1. Robot2D against the reference's printed matrices -------------------------------------------------------------------------
 def test_robot2d_forward_reproduces_the_references_printed_matrices(fb, capsys):
-    from test_reference_robot2d_linearization import check_jacobian_and_design
+    from reference_fixtures import check_jacobian_and_design
     w = fb.Robot2DWorld(64)
     lss = fb.linearize(w, None, scheme="forward")
     assert lss.A.shape == (64, 4, 4) and lss.B.shape == (64, 4, 1) and lss.C.shape == (64, 6, 4) and lss.D.shape == (64, 6, 1)
@@ -151,7 +152,7 @@ def _spread_trimmed(fb, x2, n, seed=7):
     return w
 
 
-def _scaled_err(got, want):
+def _scaled_err(got, want):   # (on purpose not support.state_scale: matrices, each system scaled by its own largest entry)
     scale = np.maximum(np.abs(want).reshape(want.shape[0], -1).max(axis=1), 1e-300)
     return (np.abs(got - want).reshape(want.shape[0], -1).max(axis=1) / scale).max()
 
@@ -193,7 +194,7 @@ def test_linearize_state_is_fb_f_ode_differenced(fb, x2, scheme, capsys):
 # ---- 4. against the oracle ---------------------------------------------------------------------------------------------------------
 def test_onesided2_matches_the_oracle(fb, oracle, capsys):
     import reference_lqr as rl
-    from test_reference_trim_points import _trim_parameters_packed   # noqa: F401  (the same node set as the LQR pins)
+    from reference_fixtures import design_trim_parameters_packed as _trim_parameters_packed   # noqa: F401  (the same node set as the LQR pins)
     n = 256
     w = _spread_trimmed(fb, False, n, seed=3)
     lss = fb.linearize_state(w, scheme="onesided2")
@@ -339,7 +340,7 @@ def _r2_world(fb, z):
 def _r2_host_linearize(fb, oracle, x, scheme):
     """the scheme applied on the host to fb_f_ode of a second Robot2D handle, which is first held to the oracle's f_ode at every point:
     xdot0 [n, 4], y0 [n, 6], A|B [n, 4, 5], C|D [n, 6, 5]"""
-    from test_oracle_robot2d import DEFAULT_VP
+    from support import DEFAULT_VP
     n = x.shape[1]
     z = x[:5]
     if scheme == "forward":
@@ -375,12 +376,6 @@ def _r2_host_linearize(fb, oracle, x, scheme):
         else:
             J[:, j] = (-3.0 * f0 + 4.0 * f[:, 1 + 2 * j] - f[:, 2 + 2 * j]) / (2.0 * H[j])
     return f0[:4].T, f0[4:].T, J[:4].transpose(2, 0, 1), J[4:].transpose(2, 0, 1)
-
-
-def _clock(fb, w):
-    cnt = C.c_int64(-1)
-    assert fb.lib.fb_get_step_count(w._h, C.byref(cnt)) == 0
-    return float(fb.lib.fb_time(w._h)), cnt.value
 
 
 @pytest.mark.parametrize("scheme", ["forward", "onesided2"])

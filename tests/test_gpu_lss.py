@@ -7,43 +7,14 @@ with the kernels. Bounds:
   1000 steps 1e-11 scaled by max(|x|, 1) per row against the longdouble RK4 (the figure the README holds the C172 stepper to), after the
              precondition that numpy fp64 stays within 1e-13 of it. Measured worst device value: docs/design/linearize.md."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
+from support import LSS_N_TRAJ as N_TRAJ, LSS_NSTEPS as NSTEPS, affine, exchange, lss_run_device as run_device, make_lss, pd as _pd, traj_case
+
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
-_D = C.POINTER(C.c_double)
-_pd = lambda a: a.ctypes.data_as(_D)
-
-
-def make_lss(fb, nx, nu, ny, n, seed, stable=False):
-    """every system of the batch has its own random matrices (a group that reads its neighbour's row shows up)"""
-    rng = np.random.default_rng(seed)
-    A = rng.standard_normal((n, nx, nx))
-    if stable:   # spectral abscissa <= -0.5 and ||A||_2 <= 5, so that ||A|| dt <= 0.05 at dt = 0.01
-        for i in range(n):
-            A[i] -= (np.linalg.eigvals(A[i]).real.max() + 0.5) * np.eye(nx)
-            A[i] *= min(1.0, 5.0 / np.linalg.norm(A[i], 2))
-            assert np.linalg.eigvals(A[i]).real.max() <= 0.0 and np.linalg.norm(A[i], 2) * 0.01 <= 0.5
-    mk = lambda *s: rng.standard_normal(s)
-    return fb.LinearizedSS(xdot0=0.1 * mk(n, nx), x0=mk(n, nx), u0=mk(n, nu), y0=mk(n, ny), A=A, B=mk(n, nx, nu), C=mk(n, ny, nx), D=mk(n, ny, nu),
-                           x_labels=tuple(f"x{k}" for k in range(nx)), u_labels=tuple(f"u{k}" for k in range(nu)),
-                           y_labels=tuple(f"y{k}" for k in range(ny)))
-
-
-def affine(c0, M, dv, N, dw, dtype=np.float64):
-    """c0 + M dv + N dw by an explicit column loop, M first; also sum of the magnitudes of every term (for the bound). [n, rows]"""
-    acc = c0.astype(dtype).copy()
-    mag = np.abs(acc)
-    for c in range(M.shape[2]):
-        t = M[:, :, c].astype(dtype) * dv[:, c:c + 1].astype(dtype)
-        acc += t; mag += np.abs(t)
-    for c in range(N.shape[2]):
-        t = N[:, :, c].astype(dtype) * dw[:, c:c + 1].astype(dtype)
-        acc += t; mag += np.abs(t)
-    return acc, mag
 
 
 def check_f_ode(fb, m, x, u):
@@ -101,63 +72,6 @@ def test_f_ode_shapes_and_batch_edges(fb, shape, n, capsys):
 
 # ---- 3. trajectories -------------------------------------------------------------------------------------------------------------------
 TRAJ_SHAPES = [(4, 1, 6), (16, 4, 33), (20, 4, 38)]
-DT, NSTEPS, N_TRAJ, STEP_AT = 0.01, 1000, 130, 100
-
-
-def rk4_host(m, x, ua, ub, dtype):
-    """the steppers' stage form, u = ua for the first STEP_AT steps and ub after them; returns x after NSTEPS. [n, nx]"""
-    A, x0 = m.A.astype(dtype), m.x0.astype(dtype)
-    x = x.astype(dtype)
-    dt, hdt, dt6 = dtype(DT), dtype(DT) / 2, dtype(DT) / 6
-    none = np.zeros((x.shape[0], 0, 0))
-    for u in (ua, ub):
-        c0, _ = affine(m.xdot0, m.B, u - m.u0, none, none, dtype)     # (held over the launch)
-        def f(z):
-            acc = c0.copy()
-            dz = z - x0
-            for c in range(A.shape[2]):
-                acc += A[:, :, c] * dz[:, c:c + 1]
-            return acc
-        for _ in range(STEP_AT if u is ua else NSTEPS - STEP_AT):
-            k1 = f(x); k2 = f(x + hdt * k1); k3 = f(x + hdt * k2); k4 = f(x + dt * k3)
-            x = x + dt6 * (2 * (k2 + k3) + (k1 + k4))
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def traj_case(fb, shape):
-    """model, start, inputs and the two host trajectories of a shape, computed once and shared (never modified)"""
-    nx, nu, ny = shape
-    m = make_lss(fb, nx, nu, ny, N_TRAJ, seed=31 * nx, stable=True)
-    rng = np.random.default_rng(nx)
-    xs = m.x0 + rng.standard_normal((N_TRAJ, nx))
-    ua, ub = m.u0 + 0.0, m.u0 + rng.standard_normal((N_TRAJ, nu))
-    x_ld = rk4_host(m, xs, ua, ub, np.longdouble)
-    x_64 = rk4_host(m, xs, ua, ub, np.float64)
-    return m, xs, ua, ub, x_ld, x_64
-
-
-def run_device(fb, case, spl, cuts=None):
-    m, xs, ua, ub = case[:4]
-    w = fb.LinearWorld(m)
-    w.set_state(xs.T)
-    w.set_params(dt=DT)
-    assert fb.lib.fb_set_steps_per_launch(w._h, spl) == 0
-    w.u = ua.T
-    for k in (cuts[0] if cuts else [STEP_AT]):
-        w.step(k)
-    w.u = ub.T
-    for k in (cuts[1] if cuts else [NSTEPS - STEP_AT]):
-        w.step(k)
-    w.sync()
-    x = w.x.T.copy()
-    cnt = C.c_int64()
-    assert fb.lib.fb_get_step_count(w._h, C.byref(cnt)) == 0 and cnt.value == NSTEPS and abs(w.t - NSTEPS * DT) < 1e-9
-    assert (w.status == 0).all()
-    w.close()
-    return x
-
-
 @pytest.mark.parametrize("shape", TRAJ_SHAPES, ids=lambda s: "%d-%d-%d" % s)
 def test_trajectory_against_longdouble_rk4(fb, shape, capsys):
     case = traj_case(fb, shape)
@@ -269,7 +183,6 @@ def _linearized_robot2d(fb):
 @pytest.mark.parametrize("name", ["panel", "shfl"])
 @pytest.mark.parametrize("source", [_linearized_x2, _linearized_robot2d], ids=["c172x2", "robot2d"])
 def test_device_to_device_construction_from_every_source(fb, source, name):
-    from test_gpu_lss_instances import exchange
     w, lss, full, sel, part = source(fb)
     rng = np.random.default_rng(5)
     with exchange(name):

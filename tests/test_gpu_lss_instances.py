@@ -22,7 +22,6 @@ those of tests/test_gpu_lss.py: the same RK4 in np.longdouble, 1000 steps of dt 
 <= 1e-11 with scale max(|x|, 1), after the precondition that numpy fp64 stays within 1e-13 of the longdouble run. The two exchanges perform the
 same operations in the same order (acc = fma(a[c], dz_c, acc), c ascending), so they have to agree bit for bit; `exchange` makes every
 world created under it prove which one it steps with (LinearWorld.exchange, fb_lss_exchange)."""
-import contextlib
 import ctypes as C
 import dataclasses
 import os
@@ -30,42 +29,13 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_lss import DT, N_TRAJ, NSTEPS, _pd, make_lss, run_device, traj_case
+from support import (LSS_DT as DT, LSS_EXCHANGE_VAR as VAR, LSS_EXCHANGES as EXCHANGES, LSS_N_TRAJ as N_TRAJ, LSS_NSTEPS as NSTEPS, clock as _clock, exchange,
+                     lss_run_device as run_device, make_lss, pd as _pd, traj_case)
 
 pytestmark = pytest.mark.gpu
-VAR = "FLIGHTBATCH_LSS_EXCHANGE"
 SHAPES = [(1, 1, 1), (4, 1, 6), (5, 2, 3), (8, 2, 3), (9, 3, 17), (16, 4, 33), (17, 4, 5), (32, 8, 64)]
-EXCHANGES = ("panel", "shfl")
 _shape_id = lambda s: "%d-%d-%d" % s
 BLOCKS = ("xdot0", "x0", "u0", "y0", "A", "B", "C", "D")
-
-
-@contextlib.contextmanager
-def exchange(name):
-    """worlds created inside step with the LDS panel ("panel") or with cross-lane reads ("shfl"): FLIGHTBATCH_LSS_EXCHANGE is read when a
-    handle is created (fb_lss_create, fb_lss_from_linearization). Every LinearWorld created inside, by whatever helper, is asked which
-    exchange it got."""
-    import flightbatch as fb
-    from flightbatch import lss as L
-    assert name in EXCHANGES
-    old = os.environ.get(VAR)
-    os.environ[VAR] = name
-    init = L.LinearWorld.__init__
-
-    def checked(self, *a, **k):
-        init(self, *a, **k)
-        assert self.exchange == name, (self.exchange, name)
-
-    L.LinearWorld.__init__ = checked
-    try:
-        yield
-    finally:
-        L.LinearWorld.__init__ = init
-        if old is None:
-            del os.environ[VAR]
-        else:
-            os.environ[VAR] = old
-    assert fb.LinearWorld is L.LinearWorld
 
 
 def first(case, k):
@@ -158,12 +128,6 @@ def _set_model(fb, w, m):
     from flightbatch.lss import pack_model
     b = pack_model(m)
     assert fb.lib.fb_lss_set_model(w._h, *[_pd(b[k]) for k in BLOCKS]) == 0, fb.lib.fb_last_error()
-
-
-def _clock(fb, w):
-    cnt = C.c_int64(-1)
-    assert fb.lib.fb_get_step_count(w._h, C.byref(cnt)) == 0
-    return float(fb.lib.fb_time(w._h)), cnt.value
 
 
 @pytest.mark.parametrize("name", EXCHANGES)

@@ -9,28 +9,9 @@ the dominant term, asserted as 1e-9 of a per-field scale; trajectories are asser
 import numpy as np
 import pytest
 
+from support import N_KIN, lattice_trim_params, q_from_euler, qmul, state_scale, stepper
+
 pytestmark = pytest.mark.gpu
-
-# per-state scale floors: quaternion components 1, rates 1e-3 rad/s
-def state_scale(x):
-    sc = np.maximum(np.abs(x), 1e-3)
-    sc[12:20] = 1.0               # q_wb, q_ew
-    sc[0:2] = np.maximum(np.abs(x[0:2]), 1e-2)   # alpha/beta filt
-    sc[2:8] = 1.0                 # contact regulators (zero airborne)
-    sc[10:12] = 1.0               # engine PI states
-    sc[20] = np.maximum(np.abs(x[20]), 1.0)
-    sc[24:27] = np.maximum(np.abs(x[24:27]), 1.0)
-    return sc
-
-
-def lattice_trim_params(fb, n, seed=172):
-    rng = np.random.default_rng(seed)
-    lat = rng.uniform(-1.2, 1.2, n); lon = rng.uniform(-np.pi, np.pi, n)
-    n_e = np.stack([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)])
-    return fb.TrimParameters(n_e=n_e, h_e=rng.uniform(200.0, 3000.0, n), EAS=rng.uniform(35.0, 55.0, n),
-                             ψ_nb=rng.uniform(-np.pi, np.pi, n), γ_wb_n=rng.uniform(-0.02, 0.02, n),
-                             ψ_wb_dot=rng.uniform(-0.03, 0.03, n), flaps=rng.choice([0.0, 0.0, 0.33], n),
-                             fuel_load=rng.uniform(0.1, 1.0, n))
 
 
 def test_trim_default_matches_oracle(fb, oracle):
@@ -382,12 +363,7 @@ def test_ground_contact_matches_oracle(fb, oracle):
     x = np.zeros((27, n))
     x[8] = 0.5
     th = rng.uniform(-0.03, 0.06, n); ph = rng.uniform(-0.03, 0.03, n); ps = rng.uniform(-np.pi, np.pi, n)
-    def qmul(a, b):
-        return np.stack([a[0]*b[0]-a[1]*b[1]-a[2]*b[2]-a[3]*b[3], a[0]*b[1]+a[1]*b[0]+a[2]*b[3]-a[3]*b[2],
-                         a[0]*b[2]-a[1]*b[3]+a[2]*b[0]+a[3]*b[1], a[0]*b[3]+a[1]*b[2]-a[2]*b[1]+a[3]*b[0]])
-    z = np.zeros(n)
-    q = qmul(qmul(np.stack([np.cos(ps/2), z, z, np.sin(ps/2)]), np.stack([np.cos(th/2), z, np.sin(th/2), z])),
-             np.stack([np.cos(ph/2), np.sin(ph/2), z, z]))
+    q = q_from_euler(ps, th, ph)
     x[12:16] = q
     lat, lon = 0.7, -0.3
     # q_ew = Rz(lon) ∘ Ry(-(lat + π/2))
@@ -502,7 +478,7 @@ def test_ecef_and_ned_mechanisations(fb, oracle, kin):
     aircraft: the three mechanisations must agree on position, attitude and velocity."""
     K = fb.K
     n = 1024
-    nk = {"ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     tp = lattice_trim_params(fb, n, seed=31)
     w = fb.BatchedWorld(n, kinematics=kin)
     fb.f_init(w, tp)
@@ -558,7 +534,6 @@ def test_approach_crosses_the_air_ground_handover(fb, oracle):
     (some down to the runway) inside fused launches: the lanes handed over to the ground-capable instance must give the same
     trajectory as the oracle, and the result must not depend on where the launch boundaries fall — 50, 7 or 1 step per launch — nor on
     which airborne stepper hands the lanes over (k_step_duo, or the one-wave k_step_air with FLIGHTBATCH_DUO=0)."""
-    from test_gpu_duo import stepper
     n = 1024
     rng = np.random.default_rng(17)
     h_trn = 300.0
@@ -882,11 +857,7 @@ def test_ground_roll_with_steering_and_brakes_matches_oracle(fb, oracle):
     x[8] = 0.5
     th = rng.uniform(-0.01, 0.03, n); ph = rng.uniform(-0.01, 0.01, n); ps = rng.uniform(-np.pi, np.pi, n)
 
-    def qmul(a, b):
-        return np.stack([a[0]*b[0]-a[1]*b[1]-a[2]*b[2]-a[3]*b[3], a[0]*b[1]+a[1]*b[0]+a[2]*b[3]-a[3]*b[2],
-                         a[0]*b[2]-a[1]*b[3]+a[2]*b[0]+a[3]*b[1], a[0]*b[3]+a[1]*b[2]-a[2]*b[1]+a[3]*b[0]])
-    z = np.zeros(n)
-    x[12:16] = qmul(qmul(np.stack([np.cos(ps/2), z, z, np.sin(ps/2)]), np.stack([np.cos(th/2), z, np.sin(th/2), z])), np.stack([np.cos(ph/2), np.sin(ph/2), z, z]))
+    x[12:16] = q_from_euler(ps, th, ph)
     lat, lon = -0.4, 2.1
     a = -(lat + np.pi / 2)
     x[16:20] = qmul(np.array([np.cos(lon/2), 0, 0, np.sin(lon/2)])[:, None] * np.ones(n), np.array([np.cos(a/2), 0, np.sin(a/2), 0])[:, None] * np.ones(n))
@@ -945,7 +916,7 @@ def test_f_step_in_the_other_mechanisations(fb, oracle, kin):
     renormalise (:409) — with the stall hysteresis, the engine's state machine and the regulator resets, against the oracle."""
     K = fb.K
     n = 512
-    nk = {"ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     w = fb.BatchedWorld(n, kinematics=kin)
     fb.f_init(w, lattice_trim_params(fb, n, seed=5))
     rng = np.random.default_rng(4)
@@ -985,15 +956,12 @@ def test_ground_contact_with_off_norm_attitude_states(fb, oracle, kin):
     force for ECEF here."""
     K = fb.K
     n = 768
-    nk = {"WA": 9, "ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     rng = np.random.default_rng(29)
 
-    def qmul(a, b):
-        return np.stack([a[0]*b[0]-a[1]*b[1]-a[2]*b[2]-a[3]*b[3], a[0]*b[1]+a[1]*b[0]+a[2]*b[3]-a[3]*b[2],
-                         a[0]*b[2]-a[1]*b[3]+a[2]*b[0]+a[3]*b[1], a[0]*b[3]+a[1]*b[2]-a[2]*b[1]+a[3]*b[0]])
     z = np.zeros(n); one = np.ones(n)
     th = rng.uniform(-0.05, 0.10, n); ph = rng.uniform(-0.12, 0.12, n); ps = rng.uniform(-np.pi, np.pi, n)
-    q_nb = qmul(qmul(np.stack([np.cos(ps/2), z, z, np.sin(ps/2)]), np.stack([np.cos(th/2), z, np.sin(th/2), z])), np.stack([np.cos(ph/2), np.sin(ph/2), z, z]))
+    q_nb = q_from_euler(ps, th, ph)
     lat, lon = 0.35, 2.4
     a = -(lat + np.pi / 2)
     q_en = qmul(np.stack([np.cos(lon/2) * one, z, z, np.sin(lon/2) * one]), np.stack([np.cos(a/2) * one, z, np.sin(a/2) * one, z]))   # ltf: Rz(lon) ∘ Ry(-(lat + π/2))

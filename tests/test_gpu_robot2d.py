@@ -3,16 +3,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_oracle_robot2d import DEFAULT_VP, gains_from_h5, run
+from support import DEFAULT_VP, gains_from_h5, robot2d_oracle_init as oracle_init, robot2d_oracle_run as run
 
 pytestmark = pytest.mark.gpu
 _D = C.POINTER(C.c_double)
-
-
-def oracle_init(L, vp, ip):
-    r = np.zeros((10, ip.shape[1]))
-    L.fo_robot2d_init(C.c_int64(ip.shape[1]), vp.ctypes.data_as(_D), np.ascontiguousarray(ip).ctypes.data_as(_D), r.ctypes.data_as(_D))
-    return r
 
 
 @pytest.mark.parametrize("dtype,tol", [("f64", 1e-11), ("f32", 2e-3)])

@@ -5,7 +5,6 @@ Every case runs N = 300 aircraft (two workgroups, the second with 44 lanes: one 
 per-aircraft parameters drawn so that the lanes of a wave sit in different phases at the same step — the ballot-gated evaluation of f_ode! and
 the mixed walk are exercised only then. The host side of every bit-for-bit comparison is the SAME table run by
 flightbatch.scenario.evaluate_on_host from a Simulation(user_callback=...), with fb.f_ode + mdl.y where the table reads vehicle.y."""
-import ctypes as C
 import io
 import os
 import sys
@@ -13,14 +12,13 @@ import sys
 import numpy as np
 import pytest
 
+from support import (assert_same_run, lattice_trim_params, load_scenario_blob as _load, run_table_on_device, same as _same, scenario_result, state_scale,
+                     table_state)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, DT = 300, 0.02
 KINS = ["WA", "ECEF", "NED"]
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 # ---- the tables -------------------------------------------------------------------------------------------------------------------------
@@ -88,12 +86,9 @@ def outputs_for_table(K, y):
                 on_gnd=((y[ldg + 1] + y[ldg + 12] + y[ldg + 23]) > 0).astype(np.float64))
 
 
-def table_state(n, scn, par, rec_init=np.nan):
-    return dict(phase=np.zeros(n, np.int64), since=np.zeros(n, np.int64), step=0, rec=np.full((scn.n_rec, n), rec_init), par=np.array(par, dtype=np.float64))
-
-
 def run_callback(fb, w, scn, par, steps, reads_y):
-    """the table as the host closure: after EVERY step, on the model's own arrays (and its outputs from fb.f_ode where the table reads them)"""
+    """the table as the host closure: after EVERY step, on the model's own arrays (and its outputs from fb.f_ode where the table reads them) — this
+    file's own form of support.run_table_as_callback, which leaves the fetching to flightbatch.scenario.host_callback"""
     from flightbatch import scenario as sc
     blob = scn.pack(model="Cessna172Sv0")
     st = table_state(w.n, scn, par)
@@ -109,24 +104,7 @@ def run_callback(fb, w, scn, par, steps, reads_y):
         mdl.u = u; mdl.ui = ui
     sim = fb.Simulation(w, dt=DT, save_on=False, user_callback=callback)
     fb.step(sim, steps * DT); w.sync()
-    return dict(x=w.x, s=w.s, u=w.u, ui=w.ui, status=w.status, phase=st["phase"].astype(np.int32), since=st["since"], rec=st["rec"])
-
-
-def run_device(fb, w, scn, par, steps, spl=50, every=1):
-    sim = fb.Simulation(w, dt=DT, save_on=False, steps_per_launch=spl)
-    w.set_scenario(scn, params=par, every=every, rec_init=np.nan)
-    fb.step(sim, steps * DT); w.sync()
-    return device_result(w)
-
-
-def device_result(w):
-    st = w.scenario_state()
-    return dict(x=w.x, s=w.s, u=w.u, ui=w.ui, status=w.status, phase=st["phase"], since=st["since"], rec=st["rec"])
-
-
-def assert_same_run(a, b, label):
-    for k in ("x", "s", "u", "ui", "status", "phase", "since", "rec"):
-        assert _same(a[k], b[k]), (label, k, np.flatnonzero((np.atleast_2d(a[k]) != np.atleast_2d(b[k])).any(0))[:8])
+    return scenario_result(w, st)
 
 
 def trimmed_pair(fb, kin, tp, env_rows=False):
@@ -161,7 +139,7 @@ def pitch_device_run(fb, kin="WA", spl=50, every=1, env_rows=False, steps=PITCH_
         assert w.trim_success.all()
         fb.f_ode(w)
         par = pitch_params(rng, w.y[fb.K["FB_Y_KIN"] + 1].copy(), N)
-        out = run_device(fb, w, pitch_table(), par, steps, spl=spl, every=every)
+        out = run_table_on_device(fb, w, pitch_table(), par, steps, DT, spl=spl, every=every)
         out["par"] = par
         w.close()
         _PITCH[key] = out
@@ -169,11 +147,6 @@ def pitch_device_run(fb, kin="WA", spl=50, every=1, env_rows=False, steps=PITCH_
 
 
 # ---- 1. acceptance and refusals -----------------------------------------------------------------------------------------------------------
-def _load(fb, w, blob):
-    blob = np.ascontiguousarray(blob, dtype=np.float64)
-    return fb.lib.fb_set_table(w._h, fb.K["FB_TABLE_SCENARIO"], blob.ctypes.data_as(C.c_void_p), (C.c_int64 * 1)(blob.size), 1)
-
-
 def test_tables_load_on_cessna172sv0_and_what_it_lacks_is_refused(fb):
     from flightbatch import scenario as sc
     good = sc.Scenario(n_par=1, n_rec=1)
@@ -231,7 +204,7 @@ def test_memory_only_table_equals_the_host_callback(fb, kin):
     steps = int(np.ceil(par[4].max() / DT)) + 20
     assert steps <= 600
     a = run_callback(fb, wa, doublet_table(), par, steps, reads_y=False)
-    b = run_device(fb, wb, doublet_table(), par, steps)
+    b = run_table_on_device(fb, wb, doublet_table(), par, steps, DT)
     mid = int(par[2].mean() / DT)
     print(f"{kin}: {steps} steps; final phases {np.bincount(b['phase'], minlength=5)}; entry steps of the last phase {b['since'].min()}..{b['since'].max()} (mean t2 at step {mid})")
     assert (b["phase"] == 4).all() and (b["status"] == 0).all() and np.unique(b["since"]).size > 20
@@ -266,7 +239,6 @@ def test_takeoff_table_on_the_ground_equals_the_host_callback_and_lifts_off_in_o
     later and with less elevator (payload and elevator are monotone in v_r), so the lift-off times are ordered like v_r: asserted on the CPU oracle
     stepped with the same table first, then on the device — which also equals the host callback bit for bit."""
     from flightbatch import scenario as sc
-    from test_gpu_parity import lattice_trim_params
     K = fb.K
     steps = 520
     rng = np.random.default_rng(0)
@@ -309,7 +281,7 @@ def test_takeoff_table_on_the_ground_equals_the_host_callback_and_lifts_off_in_o
     for mode in ("callback", "device"):
         w = fb.BatchedWorld(N)
         w.set_state(x, s); w.u = u; w.ui = ui
-        runs.append(run_callback(fb, w, scn, par, steps, reads_y=True) if mode == "callback" else run_device(fb, w, scn, par, steps))
+        runs.append(run_callback(fb, w, scn, par, steps, reads_y=True) if mode == "callback" else run_table_on_device(fb, w, scn, par, steps, DT))
         w.close()
     a, b = runs
     check("device", b["phase"], b["rec"][0], b["status"])
@@ -324,9 +296,8 @@ def test_pitch_table_against_the_oracles_phase_machine(fb, oracle):
     step. Both start from the oracle's trim and the thresholds are formed from the oracle's trimmed θ, so every number the comparison depends on is
     made on the CPU. Entry steps and phases must be IDENTICAL, which is a fair demand because every rule that fired on the oracle was clear of its
     threshold by more than 1e-6 x scale (scale 1: an angle, a climb rate around zero, a time) at the step before and at the step of firing — asserted
-    here for all 256 — and the state agrees to the project's 1e-6 (scale vector of tests/test_gpu_dispatch_matrix.py)."""
+    here for all 256 — and the state agrees to the project's 1e-6 (support.state_scale)."""
     from flightbatch import scenario as sc
-    from test_gpu_dispatch_matrix import scale
     K = fb.K
     n = 256
     rng = np.random.default_rng(12)
@@ -361,9 +332,9 @@ def test_pitch_table_against_the_oracles_phase_machine(fb, oracle):
     assert (margin > 1e-6).all(), np.argwhere(margin <= 1e-6)
     w = fb.BatchedWorld(n)
     w.set_state(r["x"], r["s"]); w.u = r["u"]; w.ui = r["ui"]
-    b = run_device(fb, w, scn, par, PITCH_STEPS)
+    b = run_table_on_device(fb, w, scn, par, PITCH_STEPS, DT)
     w.close()
-    err = np.abs(b["x"] - xo) / scale(xo, "WA")
+    err = np.abs(b["x"] - xo) / state_scale(xo, "WA")
     print("device table against the oracle's phase machine, %d steps: max scaled state error %.2e" % (PITCH_STEPS, err.max()))
     assert (b["status"] == 0).all()
     assert np.array_equal(b["phase"], st["phase"]) and np.array_equal(b["since"], st["since"])
@@ -393,7 +364,6 @@ def test_table_on_a_handle_with_environment_rows(fb, kin):
     of the stepping kernels fly it): same arithmetic, to rounding. Same phases and entry steps; the state within the bounds
     test_crosswind_landing_wind_dispersion sets for this kind of comparison (times 0.05 s, positions 1 m) and within the project's airborne
     1e-6, scaled, which is the tighter of the two here."""
-    from test_gpu_parity import state_scale
     a = pitch_device_run(fb, kin)
     b = pitch_device_run(fb, kin, env_rows=True)
     assert np.array_equal(a["phase"], b["phase"]) and np.array_equal(a["since"], b["since"]) and (b["status"] == 0).all()
@@ -427,7 +397,7 @@ def test_scenario_state_of_a_cessna172sv0_survives_a_checkpoint(fb):
     sim2 = fb.Simulation(w2, dt=DT, save_on=False, steps_per_launch=50)
     fb.restore(sim2, ck)
     fb.step(sim2, (PITCH_STEPS - 40) * DT); w2.sync()
-    assert_same_run(ref, device_result(w2), "resumed")
+    assert_same_run(ref, scenario_result(w2), "resumed")
     w2.close()
 
 

@@ -12,19 +12,13 @@ import sys
 import numpy as np
 import pytest
 
+from support import (assert_same_run, load_scenario_blob as _load, run_table_as_callback, run_table_on_device, same as _same, scenario_result, state_scale,
+                     table_state)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, DT = 320, 0.02
 GUST_STEPS = 200
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def _load(fb, w, blob):
-    blob = np.ascontiguousarray(blob, dtype=np.float64)
-    return fb.lib.fb_set_table(w._h, fb.K["FB_TABLE_SCENARIO"], blob.ctypes.data_as(C.c_void_p), (C.c_int64 * 1)(blob.size), 1)
 
 
 def _err(fb):
@@ -64,34 +58,6 @@ def make_world(fb, model, kin, tp, env):
     return w
 
 
-def result(w, st=None):
-    st = w.scenario_state() if st is None else st
-    out = dict(x=w.x, s=w.s, u=w.u, ui=w.ui, env=w.env, status=w.status, phase=np.asarray(st["phase"]).astype(np.int32), since=np.asarray(st["since"]), rec=st["rec"])
-    if hasattr(w, "cu"):
-        out.update(cu=w.cu, cs=w.cs)
-    return out
-
-
-def assert_same_run(a, b, label):
-    for k in a:
-        assert _same(a[k], b[k]), (label, k, np.flatnonzero((np.atleast_2d(a[k]) != np.atleast_2d(b[k])).any(0))[:8])
-
-
-def run_device(fb, w, scn, par, steps, spl, every, ratio=1):
-    sim = fb.Simulation(w, dt=DT, Δt=ratio * DT, save_on=False, steps_per_launch=spl)
-    w.set_scenario(scn, params=par, every=every, rec_init=np.nan)
-    fb.step(sim, steps * DT); w.sync()
-    return result(w)
-
-
-def run_callback(fb, w, scn, par, steps, every, ratio=1):
-    from flightbatch import scenario as sc
-    st = dict(phase=np.zeros(N, np.int64), since=np.zeros(N, np.int64), step=0, par=np.array(par), rec=np.full((scn.n_rec, N), np.nan))
-    sim = fb.Simulation(w, dt=DT, Δt=ratio * DT, save_on=False, user_callback=sc.host_callback(scn.pack(), st, DT, every=every))
-    fb.step(sim, steps * DT); w.sync()
-    return result(w, st)
-
-
 _GUST = {}
 
 
@@ -100,7 +66,7 @@ def gust_device_run(fb, model="s0", kin="WA", spl=1, every=1):
     if key not in _GUST:
         tp, env, par = gust_case(fb)
         w = make_world(fb, model, kin, tp, env)
-        _GUST[key] = run_device(fb, w, gust_table(), par, GUST_STEPS, spl, every, ratio=2 if model == "x2" else 1)
+        _GUST[key] = run_table_on_device(fb, w, gust_table(), par, GUST_STEPS, DT, spl, every, ratio=2 if model == "x2" else 1)
         _GUST[key]["env0"] = env
         w.close()
     return _GUST[key]
@@ -117,7 +83,7 @@ def test_wind_table_equals_the_host_callback(fb, model, kin, spl, every):
     tp, env, par = gust_case(fb)
     b = gust_device_run(fb, model, kin, spl, every)
     w = make_world(fb, model, kin, tp, env)
-    a = run_callback(fb, w, gust_table(), par, GUST_STEPS, every, ratio=2 if model == "x2" else 1)
+    a = run_table_as_callback(fb, w, gust_table(), par, GUST_STEPS, DT, every, ratio=2 if model == "x2" else 1)
     w.close()
     fired = np.ceil(par[0] / DT / every) * every
     print(f"{model} {kin} spl {spl} every {every}: switch at steps {b['since'].min()}..{b['since'].max()} ({np.unique(b['since']).size} distinct)")
@@ -151,7 +117,7 @@ def test_tapped_airspeed_behind_an_always_wind_write(fb):
     runs = []
     for mode in ("device", "callback"):
         w = make_world(fb, "s0", "WA", tp, env)
-        runs.append(run_device(fb, w, scn, par, steps, spl=50, every=1) if mode == "device" else run_callback(fb, w, scn, par, steps, every=1))
+        runs.append(run_table_on_device(fb, w, scn, par, steps, DT, spl=50, every=1) if mode == "device" else run_table_as_callback(fb, w, scn, par, steps, DT, every=1))
         w.close()
     b, a = runs
     print(f"EAS rule fired at steps {np.nanmin(b['rec'][2]) / DT:.0f}..{np.nanmax(b['rec'][2]) / DT:.0f}; tapped EAS below the record's by "
@@ -165,9 +131,8 @@ def test_tapped_airspeed_behind_an_always_wind_write(fb):
 def test_wind_table_against_the_oracle_stepped_under_per_aircraft_environments(fb, oracle):
     """Cessna172Sv0, WA, 300 steps: the oracle is stepped one step at a time, each aircraft in its own environment, and the numpy interpreter applies
     the table to those environment rows between the steps. Both start from the oracle's trim. Scaled state error <= 1e-6 (the project's airborne
-    bound, scale vector of tests/test_gpu_dispatch_matrix.py); phases, entry steps and wind rows identical (the rules read the clock only)."""
+    bound, support.state_scale); phases, entry steps and wind rows identical (the rules read the clock only)."""
     from flightbatch import scenario as sc
-    from test_gpu_dispatch_matrix import scale
     steps = 300
     tp, env6, par = gust_case(fb, seed=9)
     scn = gust_table()
@@ -177,7 +142,7 @@ def test_wind_table_against_the_oracle_stepped_under_per_aircraft_environments(f
         r = oracle.trim(tp.pack(N), fb.TrimState(N), oracle.env_rows(env_o), threads=16)
         assert r["ok"].all()
         xo, so, uo, uio = r["x"].copy(), r["s"].copy(), r["u"].copy(), r["ui"].copy()
-        st = dict(phase=np.zeros(N, np.int64), since=np.zeros(N, np.int64), step=0, par=par.copy(), rec=np.full((scn.n_rec, N), np.nan), env=env_o)
+        st = dict(table_state(N, scn, par), env=env_o)
         status = np.zeros(N, np.int32)
         for k in range(1, steps + 1):
             xo, so, stt = oracle.step(xo, uo, uio, so, oracle.env_rows(env_o), DT, 1, threads=16)
@@ -188,9 +153,9 @@ def test_wind_table_against_the_oracle_stepped_under_per_aircraft_environments(f
     w = fb.BatchedWorld(N)
     w.env = env6
     w.set_state(r["x"], r["s"]); w.u = r["u"]; w.ui = r["ui"]
-    b = run_device(fb, w, scn, par, steps, spl=50, every=1)
+    b = run_table_on_device(fb, w, scn, par, steps, DT, spl=50, every=1)
     w.close()
-    err = np.abs(b["x"] - xo) / scale(xo, "WA")
+    err = np.abs(b["x"] - xo) / state_scale(xo, "WA")
     print("wind table against the oracle, %d steps: max scaled state error %.2e" % (steps, err.max()))
     assert (b["status"] == 0).all()
     assert np.array_equal(b["phase"], st["phase"]) and np.array_equal(b["since"], st["since"]) and _same(b["rec"], st["rec"])
@@ -242,7 +207,7 @@ def test_any_output_row_as_a_source(fb):
     scn, TAS, OMEGA = y_table(K)
     w, par = y_case(fb)
     x0, s0, u0, ui0 = w.x, w.s, w.u, w.ui
-    b = run_device(fb, w, scn, par, steps, spl=50, every=1)
+    b = run_table_on_device(fb, w, scn, par, steps, DT, spl=50, every=1)
     w.close()
     t_tas, t_om = b["rec"][2], b["rec"][3]
     print(f"engine-speed rule fired at steps {np.nanmin(t_om) / DT:.0f}..{np.nanmax(t_om) / DT:.0f}, TAS rule at {np.nanmin(t_tas) / DT:.0f}..{np.nanmax(t_tas) / DT:.0f}; "
@@ -376,7 +341,7 @@ def test_terminated_aircraft_keep_their_wind(fb):
     dead = np.array([0, 7, 63, 64, 100, 255, 256, 319])
     status[dead] = K["FB_ST_ALT_RANGE"]
     assert fb.lib.fb_set_status(w._h, status.ctypes.data_as(C.POINTER(C.c_int32))) == 0
-    b = run_device(fb, w, gust_table(), par, 30, spl=50, every=1)
+    b = run_table_on_device(fb, w, gust_table(), par, 30, DT, spl=50, every=1)
     w.close()
     alive = status == 0
     assert np.array_equal(b["status"], status)
@@ -403,7 +368,7 @@ def test_wind_table_survives_a_checkpoint(fb):
     sim2 = fb.Simulation(w2, dt=DT, save_on=False, steps_per_launch=50)
     fb.restore(sim2, ck)
     fb.step(sim2, (GUST_STEPS - 80) * DT); w2.sync()
-    assert_same_run({k: v for k, v in ref.items() if k != "env0"}, result(w2), "resumed")
+    assert_same_run({k: v for k, v in ref.items() if k != "env0"}, scenario_result(w2), "resumed")
     w2.close()
 
 

@@ -6,6 +6,8 @@ import sys
 import numpy as np
 import pytest
 
+from support import abi_to_oracle_rows, load_scenario_blob, same as _same, state_scale, table_state
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -100,10 +102,6 @@ def test_traffic_pattern_batch(fb):
 
 
 # ---- the scenarios as TABLES, interpreted on the device (flightbatch/scenario.py, csrc/scenario_kernels.hpp) ----
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 def test_crosswind_landing_device_table_equals_host_callback(fb):
     """The demo's closure as a host callback after every step (PCIe both ways, every step) and as a table interpreted by k_scenario between the
     stepping launches (nothing crosses to the host during the run): same phases, same touchdown records, same final state — bit for bit."""
@@ -140,9 +138,7 @@ def test_scenario_table_is_validated_on_the_host(fb):
     good = scn.pack()
 
     def load(blob):
-        import ctypes as C
-        blob = np.ascontiguousarray(blob, dtype=np.float64)
-        return fb.lib.fb_set_table(w._h, K["FB_TABLE_SCENARIO"], blob.ctypes.data_as(C.c_void_p), (C.c_int64 * 1)(blob.size), 1)
+        return load_scenario_blob(fb, w, blob)
 
     assert load(good) == 0
     hdr, nph = K["FB_SCN_HDR"], 2
@@ -159,8 +155,7 @@ def test_scenario_table_is_validated_on_the_host(fb):
     assert load(good) == 0, "a rejected table must leave the handle usable"
     assert fb.lib.fb_scenario_configure(w._h, -1) != 0
     sv = fb.BatchedWorld(64)
-    import ctypes as C
-    assert fb.lib.fb_set_table(sv._h, K["FB_TABLE_SCENARIO"], good.ctypes.data_as(C.c_void_p), (C.c_int64 * 1)(good.size), 1) != 0 and b"Cessna172Xv2" in fb.lib.fb_last_error()
+    assert load_scenario_blob(fb, sv, good) != 0 and b"Cessna172Xv2" in fb.lib.fb_last_error()
     sv.close(); w.close()
 
 
@@ -205,20 +200,19 @@ def test_crosswind_landing_scenario_against_the_oracles_phase_machine(fb, oracle
     import crosswind_landing as demo
     from flightbatch import scenario as sc
     from oracle_binding import OracleX
-    from test_gpu_c172x import ref_to_dev_rows, x_scale
     K = fb.K
     n, dt, t_end, t_probe = 256, 0.02, 150.0, 40.0
     gpu = demo.run(n=n, t_end=t_end, seed=11, mode="device", probe_t=t_probe)
     ic = gpu["ic"]
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     X = OracleX(oracle, fb.ctl_gains.ctl_gains_blob())
     env = oracle.default_env(); env[3] = 6.0; env[5] = demo.H_ORTH     # T_sl p_sl wind N E D h_trn surface
     o = dict(x=np.zeros((34, n)), u=ic["u"].copy(), ui=ic["ui"].copy(), s=ic["s"].copy(), cu=ic["cu"].copy(), cs=ic["cs"].copy(),
              status=np.zeros(n, np.int32), nstep=0)
     o["x"][perm] = ic["x"]
-    blob = demo.scenario_table(False).pack()
-    st = dict(phase=np.zeros(n, np.int64), since=np.zeros(n, np.int64), step=0, rec=np.full((3, n), np.nan),
-              par=np.concatenate([ic["far"], ic["p2"], ic["EAS"][None], np.full((1, n), ic["p_rwy"][2]), ic["s0"][None]]))
+    scn = demo.scenario_table(False)
+    blob = scn.pack()
+    st = table_state(n, scn, np.concatenate([ic["far"], ic["p2"], ic["EAS"][None], np.full((1, n), ic["p_rwy"][2]), ic["s0"][None]]))
     x_probe = None
     nsteps = int(round(t_end / dt))
     for k in range(1, nsteps + 1):
@@ -231,7 +225,7 @@ def test_crosswind_landing_scenario_against_the_oracles_phase_machine(fb, oracle
         if k == int(round(t_probe / dt)):
             x_probe = o["x"][perm].copy()
     assert (gpu["status"] == 0).all() and (o["status"] == 0).all()
-    err = np.abs(gpu["probe"]["x"] - x_probe) / x_scale(o["x"])[perm]
+    err = np.abs(gpu["probe"]["x"] - x_probe) / state_scale(o["x"])[perm]
     print("airborne, t = %.0f s: max scaled state error %.2e" % (t_probe, err.max()))
     assert err.max() < 1e-6
     assert (gpu["phase"] == 3).all() and np.array_equal(gpu["phase"], st["phase"])
@@ -247,7 +241,6 @@ def test_elevator_doublet_device_table_equals_host_callback_and_the_oracle(fb, o
     sys.path.insert(0, os.path.join(ROOT, "examples"))
     import elevator_doublet as demo
     from oracle_binding import OracleX
-    from test_gpu_c172x import ref_to_dev_rows, x_scale
     K = fb.K
     a = demo.run(n=64, seed=4)
     b = demo.run(n=64, seed=4, mode="device")
@@ -260,7 +253,7 @@ def test_elevator_doublet_device_table_equals_host_callback_and_the_oracle(fb, o
     fb.init(sim, fb.TrimParameters(EAS=rng.uniform(40.0, 52.0, n), h_e=rng.uniform(500.0, 2500.0, n)))
     amp = rng.uniform(0.05, 0.1, n)
     assert np.array_equal(amp, a["amp"])
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     X = OracleX(oracle, fb.ctl_gains.ctl_gains_blob())
     env = oracle.default_env()
     o = dict(x=np.zeros((34, n)), u=w.u, ui=w.ui, s=w.s, cu=w.cu, cs=w.cs, status=np.zeros(n, np.int32), nstep=0)
@@ -270,7 +263,7 @@ def test_elevator_doublet_device_table_equals_host_callback_and_the_oracle(fb, o
         X.step(o, env, dt, 1, 1, threads=16)
         t = k * dt
         o["cu"][K["FB_CU_ELEVATOR_OFFSET"]] = amp if 5 <= t < 7 else (-amp if 7 <= t < 9 else 0.0)
-    err = np.abs(b["x"] - o["x"][perm]) / x_scale(o["x"])[perm]
+    err = np.abs(b["x"] - o["x"][perm]) / state_scale(o["x"])[perm]
     print("elevator doublet, 64 aircraft x 1000 steps, device table against the oracle with the closure: max scaled error %.2e" % err.max())
     assert err.max() < 1e-6 and (o["status"] == 0).all()
     dq = np.abs(b["x"][K["FB_X2_KIN"] + 8] - a["x"][K["FB_X2_KIN"] + 8]).max()

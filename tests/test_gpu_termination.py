@@ -11,7 +11,6 @@ every aircraft of a batch driven into each termination:
     * and on everything that is still flying, as before.
 """
 import ctypes as C
-import hashlib
 
 import numpy as np
 import pytest
@@ -19,38 +18,11 @@ import pytest
 import conditioning
 
 from oracle_binding import OracleX
-from test_gpu_parity import lattice_trim_params, state_scale
-from test_gpu_c172x import ref_to_dev_rows, x_scale
-from test_gpu_duo import stepper
+from support import (DEFAULT_VP, N_KIN, abi_to_oracle_rows, digest_dict, flying_batch, gains_from_h5, geoid, q_ew_from_latlon, q_from_euler,
+                     robot2d_oracle_init as oracle_init, state_scale, stepper)
 
 pytestmark = pytest.mark.gpu
 _D = C.POINTER(C.c_double)
-
-
-def qmul(a, b):
-    return np.stack([a[0]*b[0]-a[1]*b[1]-a[2]*b[2]-a[3]*b[3], a[0]*b[1]+a[1]*b[0]+a[2]*b[3]-a[3]*b[2],
-                     a[0]*b[2]-a[1]*b[3]+a[2]*b[0]+a[3]*b[1], a[0]*b[3]+a[1]*b[2]-a[2]*b[1]+a[3]*b[0]])
-
-
-def q_wb_from_euler(ps, th, ph):
-    z = np.zeros_like(ps)
-    return qmul(qmul(np.stack([np.cos(ps/2), z, z, np.sin(ps/2)]), np.stack([np.cos(th/2), z, np.sin(th/2), z])),
-                np.stack([np.cos(ph/2), np.sin(ph/2), z, z]))
-
-
-def q_ew_from_latlon(lat, lon):
-    """q_ew = Rz(lon) ∘ Ry(-(lat + π/2)) (wander angle 0)"""
-    a = -(lat + np.pi / 2)
-    z = np.zeros_like(lat)
-    return qmul(np.stack([np.cos(lon/2), z, z, np.sin(lon/2)]), np.stack([np.cos(a/2), z, np.sin(a/2), z]))
-
-
-def geoid(oracle, lat, lon):
-    out = np.zeros_like(lat)
-    for k in range(lat.size):
-        n_e = np.array([np.cos(lat[k]) * np.cos(lon[k]), np.cos(lat[k]) * np.sin(lon[k]), np.sin(lat[k])])
-        out[k] = oracle.lib.fo_geoid_height(n_e.ctypes.data_as(_D))
-    return out
 
 
 def compare_terminated(fb, w, xo, so, sto, tstep_o, twhere_o, label, min_terminated=1000, tol=1e-6):
@@ -84,7 +56,7 @@ def ground_batch(fb, oracle, n, seed, sink):
     x = np.zeros((27, n))
     x[8] = 0.5
     th = rng.uniform(-0.02, 0.08, n); ph = rng.uniform(-0.03, 0.03, n); ps = rng.uniform(-np.pi, np.pi, n)
-    x[12:16] = q_wb_from_euler(ps, th, ph)
+    x[12:16] = q_from_euler(ps, th, ph)
     lat = np.full(n, 0.7); lon = np.full(n, -0.3)
     x[16:20] = q_ew_from_latlon(lat, lon)
     x[20] = geoid(oracle, lat[:1], lon[:1])[0] + rng.uniform(2.2, 4.0, n)     # terrain at 0 m orthometric; gear legs ~1.9 m long
@@ -119,25 +91,6 @@ def test_ground_crash_on_hard_landings(fb, oracle, spl):
     fb.step(sim, 0.1); w.sync()
     assert np.array_equal(xa[:, term], w.x[:, term]) and np.array_equal(sa[:, term], w.s[:, term])
     w.close()
-
-
-def flying_batch(fb, oracle, n, seed, lat, lon, h_e, climb, env_kw):
-    """trimmed aircraft (device trim at a benign altitude) moved to altitude h_e with a vertical speed `climb` (m/s, + up)"""
-    rng = np.random.default_rng(seed)
-    tp = fb.TrimParameters(EAS=rng.uniform(40.0, 55.0, n), h_e=1000.0, ψ_nb=rng.uniform(-np.pi, np.pi, n))
-    w = fb.BatchedWorld(n)
-    fb.f_init(w, tp)
-    assert w.trim_success.all()
-    x, s, u, ui = w.x, w.s, w.u, w.ui
-    w.close()
-    x[16:20] = q_ew_from_latlon(lat, lon)
-    x[20] = h_e
-    # pitch the velocity vector: v_eb_b keeps its trimmed body components, the attitude is pitched by asin(climb / V) about body y
-    V = np.sqrt(x[24] ** 2 + x[25] ** 2 + x[26] ** 2)
-    dth = np.arcsin(np.clip(climb / V, -0.9, 0.9))
-    z = np.zeros(n)
-    x[12:16] = qmul(x[12:16], np.stack([np.cos(dth / 2), z, np.sin(dth / 2), z]))
-    return x, s, u, ui
 
 
 def run_range_case(fb, oracle, x, s, u, ui, env_kw, nsteps, spl, label, bit):
@@ -210,8 +163,6 @@ def test_isa_ceiling(fb, oracle, spl):
 
 def test_robot2d_lost_balance_matches_oracle(fb, oracle):
     """LostBalance out of f_step! (robot2d.jl:553-561): x = x_k right after the RK update, no f_periodic! in that step."""
-    from test_oracle_robot2d import DEFAULT_VP, gains_from_h5
-    from test_gpu_robot2d import oracle_init
     n = 4096
     rng = np.random.default_rng(53)
     w = fb.Robot2DWorld(n)
@@ -251,10 +202,7 @@ _X2_ORACLE = {}   # (test, ratio, digest of the start state) -> the oracle's run
 
 
 def _x2_oracle(tag, ratio, start, make):
-    h = hashlib.sha256()
-    for k in sorted(start):
-        h.update(k.encode()); h.update(np.ascontiguousarray(start[k]).tobytes())
-    key = (tag, ratio, h.hexdigest())
+    key = (tag, ratio, digest_dict(start))
     if key not in _X2_ORACLE:
         _X2_ORACLE[key] = make()
     return _X2_ORACLE[key]
@@ -288,7 +236,7 @@ def test_x2_crash_under_autopilot(fb, oracle, spl, duo, ratio):
     cu[K["FB_CU_CLM_REF"]] = -rng.uniform(7.0, 15.0, n)
     w.cu = cu
     o["cu"] = np.ascontiguousarray(cu.copy())
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     o["x"][perm] = w.x; o["cs"] = w.cs; o["u"] = w.u; o["ui"] = w.ui; o["s"] = w.s
     fb.step(sim, 12.0); w.sync()
     o_start = {k: np.array(v, copy=True) for k, v in o.items() if isinstance(v, np.ndarray)}
@@ -312,7 +260,7 @@ def test_x2_crash_under_autopilot(fb, oracle, spl, duo, ratio):
     assert np.array_equal(twhere, o["term_where"]) and np.array_equal(tstep, o["term_step"])
     assert (sto[term] == K["FB_ST_GROUND_CRASH"]).all() and (twhere[term] == K["FB_TERM_F_STEP"]).all()
     xo = o["x"][perm]
-    sc = x_scale(o["x"])[perm]
+    sc = state_scale(o["x"])[perm]
     err = np.abs(w.x - xo) / sc
     he_row = int(np.where(perm == 20)[0][0])
     flying = ~term & (xo[he_row] - N0 > 8.0)          # still clear of the runway at the end
@@ -329,7 +277,7 @@ def test_x2_crash_under_autopilot(fb, oracle, spl, duo, ratio):
     assert cerr[:, term | flying].max() < 1e-6, cerr[:, term | flying].max()
     if rolling.any():
         def lane_err(xx, cc):
-            return np.maximum((np.abs(xx - o["x"]) / x_scale(o["x"])).max(0), (np.abs(cc - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0))
+            return np.maximum((np.abs(xx - o["x"]) / state_scale(o["x"])).max(0), (np.abs(cc - o["cs"]) / np.maximum(np.abs(o["cs"]), 1.0)).max(0))
         E = np.stack([lane_err(p["x"], p["cs"])[rolling] for p in pert])
         conditioning.check_against_envelope(np.maximum(err.max(0), cerr.max(0))[rolling], E, label + ", rolling survivors")
     assert np.array_equal(w.s, o["s"])
@@ -346,7 +294,7 @@ def test_steep_descents_into_the_ground_in_every_mechanisation(fb, oracle, kin):
     ECEF aircraft ended 6·10⁻⁵ away from the oracle (found by the 10 000-step ECEF soak, tools/soak_duo.py)."""
     K = fb.K
     n = 4096
-    nk = {"WA": 9, "ECEF": 8, "NED": 6}[kin]
+    nk = N_KIN[kin]
     rng = np.random.default_rng(83)
     h_trn = 120.0
     lat, lon = 0.6, -1.1
@@ -446,7 +394,7 @@ def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, ora
     sim = fb.Simulation(w, dt=0.01, Δt=0.01 * ratio, save_on=False, steps_per_launch=spl)
     fb.init(sim, tp)
     assert w.trim_success.all()
-    perm = ref_to_dev_rows(K)
+    perm = abi_to_oracle_rows(K, "x2")
     thrower = rng.random(n) < 0.5
     xw = w.x
     he_row = int(np.where(perm == 20)[0][0])
@@ -488,7 +436,7 @@ def test_x2_survivors_sharing_a_wave_with_a_thrower_keep_their_actuators(fb, ora
     tstep, twhere = w.termination
     assert np.array_equal(twhere, o["term_where"]) and np.array_equal(tstep, o["term_step"])
     xo = o["x"][perm]
-    err = np.abs(w.x - xo) / x_scale(o["x"])[perm]
+    err = np.abs(w.x - xo) / state_scale(o["x"])[perm]
     act_rows = [int(np.where(perm == 27 + k)[0][0]) for k in range(7)]
     moved = np.abs(o["x"][27:34] - act0).max(0)
     live = ~term

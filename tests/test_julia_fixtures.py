@@ -9,18 +9,12 @@ import numpy as np
 import pytest
 
 from golden import from_julia
+from support import state_scale
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SKIP = ("no Julia-generated fixtures in tests/golden/julia/ (run `julia --project tools/gen_golden.jl tests/golden/julia` in a Flight.jl "
         "checkout); parity is checked against the C++ oracle only")
 TOL = 1e-6
-
-
-def state_scale(x):
-    sc = np.maximum(np.abs(x), 1e-3)
-    sc[..., 12:20] = 1.0; sc[..., 2:8] = 1.0; sc[..., 10:12] = 1.0
-    sc[..., 0:2] = np.maximum(np.abs(x[..., 0:2]), 1e-2); sc[..., 24:27] = np.maximum(np.abs(x[..., 24:27]), 1.0)
-    return sc
 
 
 def oracle_config1(oracle, x0=None):
@@ -39,7 +33,7 @@ def compare_config1(ref: dict, got: dict, what: str):
     """ref: from_julia.load(); got: x0 [27], traj [11, 27], xdot_end [27] of the implementation under test"""
     e0 = np.abs(got["x0"] - ref["x0"]) / state_scale(ref["x0"])
     assert e0.max() < TOL, f"{what}: trim state differs from the reference by {e0.max():.3e} (row {e0.argmax()})"
-    et = np.abs(got["traj"] - ref["traj"]) / state_scale(ref["traj"])
+    et = np.abs(got["traj"] - ref["traj"]) / state_scale(ref["traj"].T).T
     assert et.max() < TOL, f"{what}: trajectory differs from the reference by {et.max():.3e} at (sample, row) {np.unravel_index(et.argmax(), et.shape)}"
     if "xdot_end" in ref:
         ed = np.abs(got["xdot_end"] - ref["xdot_end"]) / np.maximum(np.abs(ref["xdot_end"]), 1.0)

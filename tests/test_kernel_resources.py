@@ -1,37 +1,16 @@
 """Register, scratch and LDS budgets of the built kernels, read from the code object inside the library (no GPU needed): a guard against the
 kind of regression round 6 found twice — row addresses hoisted out of a loop and spilled (948 B of scratch in the ground-capable Cessna172Xv2
 pass, 1 168 B in k_trim), which costs nothing in correctness and a great deal in time (profiles/r06_ground_launch_anatomy.txt, r06_ab_trim.txt)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "flight.jl_amd", "libflightbatch.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
+from support import library_kernels
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    if not os.path.exists(LIB):
-        pytest.fail("libflightbatch.so is not built: python -c 'import __graft_entry__ as g; g.build()'")
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
-        if not os.path.exists(os.path.join(LLVM, tool)):
-            pytest.skip(f"{tool} not found under {LLVM}")
-    d = tmp_path_factory.mktemp("co")
-    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
-    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", LIB, os.path.join(d, "discard.so")], check=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    recs = re.findall(r"\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)", notes, re.S)
-    filt = shutil.which("c++filt")
-    out = {}
-    for lds, name, scratch, vgpr in recs:
-        dem = subprocess.run([filt, name], capture_output=True, text=True).stdout.strip() if filt else name
-        out[re.sub(r"\(.*", "", dem).replace("void ", "")] = dict(lds=int(lds), scratch=int(scratch), vgpr=int(vgpr))
-    return out
+    return library_kernels(tmp_path_factory)
 
 
 def test_every_stepping_instance_is_in_the_library(kernels):

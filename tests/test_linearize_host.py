@@ -33,8 +33,8 @@ def test_header_declares_and_library_exports_the_verbs():
 
 
 def test_kernels_are_in_the_library_without_scratch(tmp_path_factory):
-    import test_kernel_resources as kr
-    ks = kr.kernels.__wrapped__(tmp_path_factory)
+    from support import library_kernels
+    ks = library_kernels(tmp_path_factory)
     want = ["fbd::k_lin_base<false>", "fbd::k_lin_base<true>", "fbr::k_r2_lin_base"]
     want += [f"fbd::k_lin_diff<{x}, 0, 0>" for x in ("false", "true")]
     want += [f"fbd::k_lin_diff<{x}, 1, {p}>" for x in ("false", "true") for p in (0, 1)]

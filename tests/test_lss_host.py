@@ -80,8 +80,8 @@ def test_packing_round_trips_the_abi_layout(fb):
 
 def test_lss_and_lqr_kernels_are_in_the_library(tmp_path_factory):
     """the instances lss_with_group and the LQR dispatcher launch, with the scratch and LDS docs/design/linearize.md tabulates"""
-    import test_kernel_resources as kr
-    ks = kr.kernels.__wrapped__(tmp_path_factory)
+    from support import library_kernels
+    ks = library_kernels(tmp_path_factory)
     where = "the table of instances is the docstring of tests/test_gpu_lss_instances.py: an instance added or removed gets its row there"
     groups = (4, 8, 16, 32)
     lds = {f"fbl::k_lss_rk4<{g}, {x}>": 2048 * (1 - x) for g in groups for x in (0, 1)}

@@ -10,25 +10,12 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flight.jl_amd", "flightbatch"))
 from oracle_binding import OracleX, header_enums  # noqa: E402
+from support import default_trim_params, default_trim_state, seg_end  # noqa: E402
 
 K = header_enums()
 _D = C.POINTER(C.c_double)
 Y_W_WB_B, Y_V_EB_B, Y_V_EB_N, Y_THETA, Y_PHI, Y_H_E, Y_CHI = K["FB_Y_KIN"] + 25, K["FB_Y_KIN"] + 31, K["FB_Y_KIN"] + 34, 1, 2, K["FB_Y_KIN"] + 20, K["FB_Y_KIN"] + 38
 Y_EAS, Y_BETA = K["FB_Y_AIR"] + 20, K["FB_Y_AERO"] + 1
-
-
-def default_trim_params(n=1, **kw):
-    tp = np.zeros((K["FB_NTP"], n))
-    tp[K["FB_TP_N_E"]] = 1.0; tp[K["FB_TP_H_E"]] = 1050.0; tp[K["FB_TP_EAS"]] = 50.0
-    tp[K["FB_TP_FUEL_LOAD"]] = 0.5; tp[K["FB_TP_MIXTURE"]] = 0.5
-    tp[K["FB_TP_PAYLOAD"]:K["FB_TP_PAYLOAD"] + 5] = np.array([75.0, 75.0, 0.0, 0.0, 50.0])[:, None]
-    for k, v in kw.items():
-        tp[K[k]] = v
-    return tp
-
-
-def default_trim_state(n=1):
-    return np.tile(np.array([[0.08], [0.0], [0.75], [0.4], [0.0], [0.0], [0.0]]), (1, n))
 
 
 @pytest.fixture(scope="module")
@@ -242,12 +229,6 @@ def test_altitude_acquire_and_hold(oracle, gains):
 
 
 # ---- guidance: lib/FlightApps/test/c172/test_c172x2.jl --------------------------------------------------------------
-def seg_end(oracle, p1, s, chi, dh):
-    p1 = np.asarray(p1, dtype=np.float64); p2 = np.zeros(3)
-    oracle.lib.fo_segment_end(p1.ctypes.data_as(_D), C.c_double(s), C.c_double(chi), C.c_double(dh), p2.ctypes.data_as(_D))
-    return p2
-
-
 def seg_data(oracle, p1, p2, ob):
     out = np.zeros(8)
     a, b, c = (np.asarray(v, dtype=np.float64) for v in (p1, p2, ob))

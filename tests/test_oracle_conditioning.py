@@ -9,7 +9,7 @@ import pytest
 
 import conditioning
 from oracle_binding import OracleX, header_enums
-from test_oracle_c172x import default_trim_params, default_trim_state
+from support import default_trim_params, default_trim_state
 
 K = header_enums()
 
@@ -22,7 +22,7 @@ def gains():
     return ctl_gains.ctl_gains_blob()
 
 
-def scaled(x):
+def scaled(x):   # (on purpose not support.state_scale: plain max(|x|, 1) on the 27 vehicle rows — the oracle against itself, on the ground)
     sc = np.ones_like(x)
     sc[:27] = np.maximum(np.abs(x[:27]), 1.0)
     sc[16:20] = 1.0

@@ -1,36 +1,10 @@
 """Pins the Robot2D oracle against the reference's own tests: lib/FlightApps/test/robot2d/test_robot2d.jl:19-64 (vehicle)
 and :70-102 (closed loop with the LQR/PID controller and the gains of robot2d.h5)."""
 import ctypes as C
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "flight.jl_amd", "flightbatch"))
-_D = C.POINTER(C.c_double)
-_I = C.POINTER(C.c_int32)
-
-
-def dp(a):
-    return a.ctypes.data_as(_D)
-
-
-DEFAULT_VP = np.array([0.15, 0.05, 1.0, 0.1, -1.0, -1.0, 0.32, 0.0189, 0.0014])
-
-
-def gains_from_h5():
-    import hdf5_min
-    d = hdf5_min.read_all(os.path.join(ROOT, "flight.jl_amd", "data", "robot2d.h5"))
-    return np.concatenate([d["K_fbk"].ravel(), d["K_fwd"].ravel(), d["K_int"].ravel(), d["x_trim"].ravel(), d["u_trim"].ravel(),
-                           d["z_trim"].ravel(), [0.6, 0.0, 0.0, 0.01]]).astype(np.float64)
-
-
-def run(L, vp, gp, r, u, dt, ratio, ctl, step0, nsteps):
-    st = np.zeros(r.shape[1], np.int32)
-    L.fo_robot2d_step(C.c_int64(r.shape[1]), dp(vp), dp(gp), C.c_double(dt), ratio, ctl, dp(u), dp(r), C.c_int64(step0), C.c_int64(nsteps),
-                      st.ctypes.data_as(_I))
-    return st
+from support import DEFAULT_VP, gains_from_h5, pd as dp, robot2d_oracle_run as run
 
 
 def test_hdf5_gains_file():

@@ -133,7 +133,7 @@ def test_crash_in_f_step_leaves_the_part_of_f_step_that_ran(fb, oracle):
 
 
 def test_robot2d_lost_balance_stops_after_the_rk_update(fb, oracle):
-    from test_oracle_robot2d import DEFAULT_VP, gains_from_h5
+    from support import DEFAULT_VP, gains_from_h5
     n = 64
     vp = DEFAULT_VP.copy(); gp = gains_from_h5()
     r = np.zeros((10, n)); r[2] = np.linspace(0.5, 0.78, n)                         # tilted, motor command 0: falls

@@ -6,19 +6,15 @@ must also trim from the default guess."""
 import ctypes as C
 import numpy as np
 
+from support import default_trim_params
+
 TS0 = np.array([0.1, 0.0, 0.75, 0.47, 0.014, -0.0015, 0.02])   # TrimState() defaults, c172.jl:796-804
-
-
-def default_tp(n):
-    tp = np.zeros((18, n)); tp[0] = 1; tp[3] = 1050; tp[5] = 50; tp[10] = 0.5; tp[11] = 0.5
-    tp[13:18] = np.array([75, 75, 0, 0, 50.0])[:, None]      # PayloadY() defaults
-    return tp
 
 
 def bench_lattice_tp():
     """the 32 x 32 (EAS, h) cells of bench.py's config-3 lattice (heading 0)"""
     i, j = np.meshgrid(np.arange(32), np.arange(32), indexing="ij")
-    tp = default_tp(1024)
+    tp = default_trim_params(1024)
     tp[5] = (35.0 + 20.0 * i / 31.0).ravel(); tp[3] = (200.0 + 2800.0 * j / 31.0).ravel()
     return tp
 
@@ -58,7 +54,7 @@ def test_success_set_is_the_flight_envelope(oracle):
     trim that parameter continuation from TrimParameters() reaches."""
     i, j = np.meshgrid(np.arange(40), np.arange(24), indexing="ij")
     n = i.size
-    tp = default_tp(n)
+    tp = default_trim_params(n)
     EAS = (25.0 + 45.0 * i / 39.0); h = (150.0 + 5850.0 * j / 23.0)
     tp[5] = EAS.ravel(); tp[3] = h.ravel()
     env = oracle.default_env()
@@ -110,7 +106,7 @@ def test_per_aircraft_environment_equals_one_call_per_aircraft(oracle):
     and 200 steps, bit for bit."""
     n = 16
     rng = np.random.default_rng(4)
-    tp = default_tp(n)
+    tp = default_trim_params(n)
     tp[5] = rng.uniform(38, 52, n); tp[3] = rng.uniform(300, 2500, n); tp[4] = rng.uniform(-3, 3, n)
     env6 = np.stack([rng.uniform(-10, 10, n), rng.uniform(-10, 10, n), rng.uniform(-1, 1, n), rng.uniform(260, 310, n), rng.uniform(97e3, 104e3, n),
                      rng.uniform(0, 100, n)])

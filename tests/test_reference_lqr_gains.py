@@ -17,7 +17,7 @@ import pytest
 
 import reference_fixtures as rf
 import reference_lqr as rl
-from test_reference_trim_points import _trim_parameters_packed
+from reference_fixtures import design_trim_parameters_packed as _trim_parameters_packed
 
 TOL = 5e-6
 pytest.importorskip("scipy.linalg")

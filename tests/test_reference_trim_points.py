@@ -17,16 +17,6 @@ import reference_fixtures as rf
 TOL = 1e-6   # absolute, every row (radians, normalised engine speed, normalised actuator positions; EAS in m/s)
 
 
-def _trim_parameters_packed(n_copies=1):
-    """C172.TrimParameters(; Ob = Geographic(LatLon(), HEllip(h)), EAS, flaps) — c172x_design.jl:107-112; LatLon() is ϕ = λ = 0,
-    i.e. n_e = (1, 0, 0); everything else at its default (c172.jl:806-818)."""
-    EAS, h, flaps = (np.tile(a, n_copies) for a in rf.design_nodes())
-    n = EAS.size
-    tp = np.zeros((18, n)); tp[0] = 1.0; tp[3] = h; tp[5] = EAS; tp[10] = 0.5; tp[11] = 0.5; tp[12] = flaps
-    tp[13:18] = np.array([75.0, 75.0, 0.0, 0.0, 50.0])[:, None]
-    return tp
-
-
 def test_shipped_data_files_are_the_references():
     import json
     for rel in json.load(open(rf.HASHES)):
@@ -44,7 +34,7 @@ def test_flaps_schedule_and_nodes():
 
 
 def test_oracle_trim_reproduces_the_references_stored_trim_points(oracle, capsys):
-    tp = _trim_parameters_packed()
+    tp = rf.design_trim_parameters_packed()
     env = oracle.default_env()
     ts0 = np.tile(np.array([0.1, 0.0, 0.75, 0.47, 0.014, -0.0015, 0.02])[:, None], (1, 28))   # TrimState(), c172.jl:796-804
     r = oracle.trim(tp, ts0, env)

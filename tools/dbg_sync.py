@@ -1,14 +1,13 @@
-import ctypes as C, os, sys, time, traceback
-import numpy as np
+import ctypes as C, sys, time
+import pytest
 sys.path.insert(0, "flight.jl_amd"); sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import flightbatch as fb
-import test_gpu_duo as T
+# usage: tools/dbg_sync.py [n spl kin]   one case of tests/test_gpu_duo.py::test_duo_and_air_steppers_agree, run in this process so that the
+# counters the kernels leave behind can be read afterwards
+case = "-".join(sys.argv[1:4]) if len(sys.argv) > 3 else "1000-50-WA"
 t0 = time.time()
-try:
-    T.test_duo_and_air_steppers_agree(fb, int(sys.argv[1]) if len(sys.argv) > 1 else 1000, int(sys.argv[2]) if len(sys.argv) > 2 else 50)
-    print("test passed")
-except BaseException:
-    traceback.print_exc(limit=2)
+rc = pytest.main(["-q", "-x", f"tests/test_gpu_duo.py::test_duo_and_air_steppers_agree[{case}]"])
+print("test passed" if rc == 0 else f"pytest exit status {int(rc)}")
 print("took", time.time() - t0)
 out = (C.c_uint * 40)()
 fb.lib.fb_debug_duo_sync(out)
