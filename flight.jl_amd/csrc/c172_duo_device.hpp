@@ -90,7 +90,15 @@ FB_KC(KC_P_SQRT_T_STD, isa_sqrt_T_std); FB_KC(KC_P_P_RATED, c172::P_rated); FB_K
 FB_KC_RCP(KC_P_INV_J, c172::J_eng + c172::prop_Jxx); FB_KC_RCP(KC_P_INV_M_FUEL, c172::m_full - c172::m_res);
 FB_KC(KC_P_F_LEAN, c172::f_lean);
 
-template <int KIN, int ROLE, class In, class Emit, class XV, class KP = KLit>
+// What an instance of k_step_duo opts into, per step of "Round 8" (docs/design/k_step_duo.md; the switches sit next to duo_nk() in
+// c172_kernels.hpp). The default is the code every other instance keeps.
+//   PIN_IN_PLACE: the values a role must have read ahead of a publication are pinned THEMSELVES, as INPUTS of an empty asm ("v": the value is
+//                 in its register here, so the read has been waited for), instead of "+v" copies of them: a copy is a v_mov_b64 per value
+//                 that waits for the read and moves nothing, and a tied output cannot stay inside a ds_read2's register tuple.
+template <bool PIN_IN_PLACE_ = false>
+struct DuoOpt { static constexpr bool PIN_IN_PLACE = PIN_IN_PLACE_; };
+
+template <int KIN, int ROLE, class OPT = DuoOpt<>, class In, class Emit, class XV, class KP = KLit>
 __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state, const In& in, const Env& env, const Tables& T, const Emit& emit, StepAux& aux,
                                            const KP& K = KP{}) {   // K: role P's constants (role D passes none: literals)
     using namespace c172;
@@ -136,7 +144,11 @@ __device__ __forceinline__ int32_t rhs_duo(const XV& x, int stall, int eng_state
         lds_cptr RPT = T.rk + LDS_PISTON;
         const double w_eng = x[FB_X_ENG_OMEGA];
         const double x_frc = x[FB_X_ENG_FRC], x_idle = x[FB_X_ENG_IDLE], x_fuel = x[FB_X_FUEL];
-        {   // every state row this role reads is read HERE (pinned: the compiler may not sink a read towards its use, past the point)
+        if constexpr (OPT::PIN_IN_PLACE) {   // (the same pins on the values themselves; only the WA mechanisation opts in)
+            static_assert(!OPT::PIN_IN_PLACE || KIN == FB_KIN_WA, "PIN_IN_PLACE: the WA mechanisation's position rows");
+            asm volatile("" :: "v"(w_eng), "v"(x_frc), "v"(x_idle), "v"(x_fuel), "v"(h_e));
+            asm volatile("" :: "v"(q_ew.w), "v"(q_ew.x), "v"(q_ew.y), "v"(q_ew.z));
+        } else {   // every state row this role reads is read HERE (pinned: the compiler may not sink a read towards its use, past the point)
             double pin_w = w_eng, pin_f = x_frc, pin_i = x_idle, pin_u = x_fuel, pin_h = h_e;
             asm volatile("" : "+v"(pin_w), "+v"(pin_f), "+v"(pin_i), "+v"(pin_u), "+v"(pin_h));
             if constexpr (KIN == FB_KIN_WA) {
@@ -496,7 +508,9 @@ DUO_MARK(1, 6);   // engine head done
         const v3 F_p = {emit.xget(XD_FP), emit.xget(XD_FP + 1), emit.xget(XD_FP + 2)};
         const v3 tau_pb = {emit.xget(XD_TAUP), emit.xget(XD_TAUP + 1), emit.xget(XD_TAUP + 2)};
         const double h_rot = emit.xget(XD_HROT);   // (h_rot, 0, 0)
-        {   // (pinned: the reads above are complete at the point below)
+        if constexpr (OPT::PIN_IN_PLACE) {
+            asm volatile("" :: "v"(F_p.x), "v"(F_p.y), "v"(F_p.z), "v"(tau_pb.x), "v"(tau_pb.y), "v"(tau_pb.z), "v"(h_rot));
+        } else {   // (pinned: the reads above are complete at the point below)
             double p0 = F_p.x, p1 = F_p.y, p2 = F_p.z, p3 = tau_pb.x, p4 = tau_pb.y, p5 = tau_pb.z, p6 = h_rot;
             asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(p4), "+v"(p5), "+v"(p6));
         }

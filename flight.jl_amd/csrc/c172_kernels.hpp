@@ -1185,6 +1185,19 @@ static_assert(DUO_NDL_WA >= 1 && DUO_NDL_WA <= DUO_ND && DUO_NDL_X >= 1 && DUO_N
 // whole list (docs/design/k_step_duo.md "Round 7", profiles/r07_ab_resident_constants.txt); every other instance keeps none, and
 // its code is what it was, until an A/B of its own says otherwise.
 template <int KIN, bool X, bool PERENV> constexpr int duo_nk() { return (KIN == FB_KIN_WA && !X && !PERENV) ? (int)KC_COUNT : 0; }
+// "Round 8" (docs/design/k_step_duo.md): what else that one instance opts into, a constexpr switch per step, kept by measurement
+// (profiles/r08_ab_issue_slots.txt: together the steps clear the bar for a gain, none of them alone). Every other instance gets DuoOpt<>
+// and false for the rest: the code it had.
+constexpr bool DUO_R8_PIN_IN_PLACE = true;   // step A: pins on the values, not on copies of them
+constexpr bool DUO_R8_SUMS_STAY = true;      // step B: role D's four register-resident stage sums keep their registers through the loop
+constexpr bool DUO_R8_AERO_PANEL = true;     // step E: seven of role D's aerodynamic launch constants from an LDS panel, the two table intervals in one word
+template <int KIN, bool X, bool PERENV> constexpr bool duo_r8() { return KIN == FB_KIN_WA && !X && !PERENV; }
+// (the wave's running lanes as the evaluation's entry condition; ALWAYS: enter without asking — a helper, because any other wording of the
+// condition at its site reorders instructions in the instances that do not opt in)
+template <bool ALWAYS> __device__ __forceinline__ unsigned long long duo_run_mask(bool run) { if constexpr (ALWAYS) return 1; else return __builtin_amdgcn_ballot_w64(run); }
+template <int KIN, bool X, bool PERENV> constexpr bool duo_sums_stay() { return duo_r8<KIN, X, PERENV>() && DUO_R8_SUMS_STAY; }
+template <int KIN, bool X, bool PERENV> constexpr bool duo_aero_panel() { return duo_r8<KIN, X, PERENV>() && DUO_R8_AERO_PANEL; }
+template <int KIN, bool X, bool PERENV> using duo_opt = DuoOpt<duo_r8<KIN, X, PERENV>() && DUO_R8_PIN_IN_PLACE>;
 template <int NK>
 struct DuoK {
     double r[NK];
@@ -1235,6 +1248,31 @@ struct InputsDuoD {
     __device__ __forceinline__ static void aero_from_raw(const double (&v)[DUO_NCONST], AeroC& c) {
         c.cd_in = v[0]; c.cd_df = v[1]; c.cy_in = v[2]; c.cl_in = v[3]; c.cl_df = v[4]; c.croll_in = v[5]; c.cm_in = v[6]; c.cn_in = v[7];
         c.l_df4 = {(int)v[8], v[9]}; c.l_df2 = {(int)v[10], v[11]};
+    }
+};
+// role D's inputs with DUO_R8_AERO_PANEL: the two table intervals travel in one word (as in the Cessna172Xv2 instance's panel), seven of the eleven
+// values left come from an LDS panel of role D's own, written once at the head of the launch and read with immediate offsets (lane-contiguous
+// rows, like the payload panel: 14 336 B, the last free bytes of the LDS), and four stay in the rows of KArgs::duo_pld. In the panel: what
+// the evaluation consumes first (the flap axis' intervals and weights, the two flap terms) and cd_in, cm_in; in memory: the four sums
+// consumed last, behind role P's point A.
+struct InputsDuoDL : InputsDuoD {
+    static constexpr int NL = 7, NG = 4;
+    lds_cptr aero_l;   // &panel[lane], rows: cd_in cd_df cl_df cm_in w_df4 w_df2 | the two intervals in one word
+    __device__ __forceinline__ static void split(const AeroC& c, double (&l)[NL], double (&g)[NG]) {
+        const uint64_t iw = (uint64_t)(uint32_t)c.l_df4.i | ((uint64_t)(uint32_t)c.l_df2.i << 32);
+        l[0] = c.cd_in; l[1] = c.cd_df; l[2] = c.cl_df; l[3] = c.cm_in; l[4] = c.l_df4.w; l[5] = c.l_df2.w; l[6] = __builtin_bit_cast(double, iw);
+        g[0] = c.cy_in; g[1] = c.cl_in; g[2] = c.croll_in; g[3] = c.cn_in;
+    }
+    __device__ __forceinline__ void fetch_aero(AeroC& c) const {
+        double g[NG], l[NL];
+#pragma unroll
+        for (int k = 0; k < NG; k++) g[k] = aero_g[(int64_t)k * n];
+#pragma unroll
+        for (int k = 0; k < NL; k++) l[k] = aero_l[k * DUO_B];
+        const uint64_t iw = __builtin_bit_cast(uint64_t, l[6]);
+        c.cd_in = l[0]; c.cd_df = l[1]; c.cl_df = l[2]; c.cm_in = l[3];
+        c.l_df4 = {(int)(uint32_t)iw, l[4]}; c.l_df2 = {(int)(uint32_t)(iw >> 32), l[5]};
+        c.cy_in = g[0]; c.cl_in = g[1]; c.croll_in = g[2]; c.cn_in = g[3];
     }
 };
 // role D's inputs in the Cessna172Xv2 instance: InputsDuoD with the payload's sums in registers (fetched from memory ahead of the kinematics
@@ -1329,7 +1367,7 @@ FBD void duo_wait(DuoSync& sy, int k) {
 #endif
 }
 
-template <int ROLE, bool X = false, int NDL = DUO_ND>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
+template <int ROLE, bool X = false, int NDL = DUO_ND, bool SUMS_STAY = false>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
 struct DuoEmit {
     static constexpr int role = ROLE;
     static constexpr bool x2 = X;   // the Cessna172Xv2 instance: role D fetches the evaluation's aerodynamic sums behind role P's point R, every publication
@@ -1393,6 +1431,15 @@ struct DuoEmit {
 #pragma unroll
         for (int e = 0; e < NE; e++) {
             const int r = SV::row(j0 + e);
+            if constexpr (SUMS_STAY && ROLE == 2) {
+                if (slot(r) >= NDL) {   // a register-resident sum: its last read (the select) ahead of the product that replaces it, so that the product takes its register
+                    double sel = last ? A[e] : k[e];
+                    asm volatile("" : "+v"(sel), "+v"(A[e]));
+                    aset(r, A[e] * em);
+                    xwr_l[r * DUO_B + t] = __builtin_fma(ee, sel, xs[e]);
+                    continue;
+                }
+            }
             aset(r, A[e] * em);
             xwr_l[r * DUO_B + t] = __builtin_fma(ee, last ? A[e] : k[e], xs[e]);
         }
@@ -1683,7 +1730,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     emit.xwait(DUO_PT_X);
                     (void)xv; (void)aux; (void)inl;
 #else
-                    rhs_duo<KIN, 1>(xv, 0, eng, inl, env_p, T, emit, aux, kres);
+                    rhs_duo<KIN, 1, duo_opt<KIN, X, PERENV>>(xv, 0, eng, inl, env_p, T, emit, aux, kres);
 #endif
                     if constexpr (X) {
                         if (sk.last) {
@@ -1751,8 +1798,12 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
     // ================= role D =================
     // The lane's bookkeeping state lives in an LDS word between evaluations (D_* bits): kept in registers it is what the allocator
     // spills around the evaluation, and the reloads land in the divergent bookkeeping code (tools/check_isa_spills.py).
-    InputsDuoD in;
+    typename std::conditional<duo_aero_panel<KIN, X, PERENV>(), InputsDuoDL, InputsDuoD>::type in;
     in.pld_l = (lds_cptr)pld_l + t; in.aero_g = a.duo_pld + (valid ? i : 0); in.n = a.n; in.ui = 0;
+    if constexpr (duo_aero_panel<KIN, X, PERENV>()) {
+        __shared__ double aero_l[InputsDuoDL::NL * B];   // (declared here: only the instance that opts in has it)
+        in.aero_l = (lds_cptr)aero_l + t;
+    }
     double accd_r[ND > DUO_NDL ? ND - DUO_NDL : 1];   // the stage sums that do not live in LDS (DUO_NDL)
 #pragma unroll
     for (int k = 0; k < (ND > DUO_NDL ? ND - DUO_NDL : 1); k++) accd_r[k] = 0.0;
@@ -1791,10 +1842,23 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                 for (int k = 0; k < 3; k++) pld_l[(1 + k) * B + t] = in0.pld_Mr[k];
 #pragma unroll
                 for (int k = 0; k < 6; k++) pld_l[(4 + k) * B + t] = in0.pld_J[k];
+                if constexpr (duo_aero_panel<KIN, X, PERENV>()) {
+                    AeroC c0;
+                    c0.cd_in = in0.cd_in; c0.cd_df = in0.cd_df; c0.cy_in = in0.cy_in; c0.cl_in = in0.cl_in; c0.cl_df = in0.cl_df; c0.croll_in = in0.croll_in;
+                    c0.cm_in = in0.cm_in; c0.cn_in = in0.cn_in; c0.l_df4 = in0.l_df4; c0.l_df2 = in0.l_df2;
+                    double pl[InputsDuoDL::NL], pg[InputsDuoDL::NG];
+                    InputsDuoDL::split(c0, pl, pg);
+                    lds_ptr ap = (lds_ptr)in.aero_l;
+#pragma unroll
+                    for (int k = 0; k < InputsDuoDL::NL; k++) ap[k * B] = pl[k];
+#pragma unroll
+                    for (int k = 0; k < InputsDuoDL::NG; k++) a.duo_pld[(int64_t)k * a.n + i] = pg[k];
+                } else {
                 const double ac[DUO_NCONST] = {in0.cd_in, in0.cd_df, in0.cy_in, in0.cl_in, in0.cl_df, in0.croll_in, in0.cm_in, in0.cn_in,
                                                (double)in0.l_df4.i, in0.l_df4.w, (double)in0.l_df2.i, in0.l_df2.w};
 #pragma unroll
                 for (int k = 0; k < DUO_NCONST; k++) a.duo_pld[(int64_t)k * a.n + i] = ac[k];
+                }
                 in.ui = in0.ui;
             }
         }
@@ -1819,6 +1883,14 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
         duo_publish(sy, DUO_PT_T);   // the control and flag words of this evaluation are written, every row of the previous one emitted
         DUO_MARK(2, 0);
         if (exit_) { DUO_PHASE(3); break; }
+        if constexpr (duo_sums_stay<KIN, X, PERENV>()) {
+            if (redoing) {   // (wave-uniform; the lanes whose k1 is re-evaluated: their register sums held the discarded k1)
+                if (flags_l[t] & DUO_F_ZERO_ACC) {
+#pragma unroll
+                    for (int k = 0; k < (ND > DUO_NDL ? ND - DUO_NDL : 1); k++) accd_r[k] = 0.0;
+                }
+            }
+        }
         const StageK sk = stage_k(stage);
         int lds_off = 0;
         asm volatile("" : "+s"(lds_off));
@@ -1827,12 +1899,16 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
         aux.alpha = 0; aux.m_avail = 0; aux.wow = 0; aux.crash = 0;
         int32_t bits = 0;
         bool run = flags_l[t] & DUO_F_RUN;
-        if (__builtin_amdgcn_ballot_w64(run) != 0) {
+        // (DUO_R8_SUMS_STAY: one divergent region around the evaluation and the "nobody runs" publication behind it, instead of a uniform
+        // branch around both: the register-resident stage sums then pass ONE join per iteration and keep their registers)
+        // (no local constexpr for the switch: a declaration at this place reorders instructions in the instances that do not opt in)
+        if (duo_run_mask<duo_sums_stay<KIN, X, PERENV>()>(run) != 0) {
             if (run) {
                 const int d0 = dst_l[t];
-                typename std::conditional<X, InputsDuoDX, InputsDuoD>::type inl;
+                typename std::conditional<X, InputsDuoDX, decltype(in)>::type inl;
                 static_cast<InputsDuoD&>(inl) = in;
                 inl.aero_g = in.aero_g + lds_off; inl.pld_l = in.pld_l + lds_off;
+                if constexpr (duo_aero_panel<KIN, X, PERENV>()) inl.aero_l = in.aero_l + lds_off;
                 if constexpr (X) {
                     // base and stride of the payload rows, read from the kernel's arguments HERE, at the head of the evaluation (scalar loads that
                     // complete long before the fetch: held in SGPRs across the whole loop they are spilled)
@@ -1842,7 +1918,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     inl.aero_g = ka->duo_pld + il;
                     inl.n = ka->n;
                 }
-                const DuoEmit<2, X, DUO_NDL> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
+                const DuoEmit<2, X, DUO_NDL, duo_sums_stay<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
                                             tap_now, i};
                 const SV xv = {sk.xrd_l + t + lds_off};
 #if defined(FB_DUO_ONLY) && FB_DUO_ONLY == 1
@@ -1864,10 +1940,11 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     env_d.wind_n = e[(int64_t)FB_ENV_WIND_N * en]; env_d.wind_e = e[(int64_t)FB_ENV_WIND_E * en]; env_d.wind_d = e[(int64_t)FB_ENV_WIND_D * en];
                     env_d.h_trn = e[(int64_t)FB_ENV_H_TERRAIN * en];
                 }
-                bits = rhs_duo<KIN, 2>(xv, (d0 & D_STALL) ? 1 : 0, (d0 >> D_ENG_SHIFT) & 3, inl, env_d, T, emit, aux);
+                bits = rhs_duo<KIN, 2, duo_opt<KIN, X, PERENV>>(xv, (d0 & D_STALL) ? 1 : 0, (d0 >> D_ENG_SHIFT) & 3, inl, env_d, T, emit, aux);
 #endif
             }
         } else duo_publish(sy, DUO_PT_X);   // (an evaluation nobody runs: role P must not wait for it)
+        if constexpr (duo_sums_stay<KIN, X, PERENV>()) { if (__builtin_amdgcn_ballot_w64(run) == 0) duo_publish(sy, DUO_PT_X); }
         // (f_step!, below, modifies x_{n+1} in place at the end of a step's last evaluation: role P has read what it reads of it — its
         // point R, which this wave has waited for in the evaluation)
         int d = dst_l[t];
@@ -1916,7 +1993,9 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
 #pragma unroll
                     for (int k = 0; k < DUO_NDL; k++) accd_l[k * B + t] = 0.0;   // (acc held the discarded k1; stage 0 reads x_n from xs_l itself)
 #pragma unroll
-                    for (int k = 0; k < (ND > DUO_NDL ? ND - DUO_NDL : 1); k++) accd_r[k] = 0.0;
+                    for (int k = 0; k < (ND > DUO_NDL ? ND - DUO_NDL : 1); k++) {
+                        if constexpr (!(duo_sums_stay<KIN, X, PERENV>())) accd_r[k] = 0.0;   // (else: at the top of the re-evaluation)
+                    }
                 }
                 zero_acc = mod; run = mod; redoing = true; advance = false;
             }
