@@ -290,6 +290,28 @@ function lqr(w::LinearWorld, q::Matrix{Float64}, r::Matrix{Float64})
                 w.handle, q, r, k, x, resid, iters, status))
     return (; k, x, resid, iters, status)
 end
+"P(jω) = c inv(jωI - A) b + d of channel (iu, iy) (1-based) of every system of `w` on the grid `freqs` (rad/s, positive), on its device: the
+plant of `sensitivity(plant, pid)` (FA design/pidopt.jl:39). Returns (re, im), each N x length(freqs)."
+function freqresp(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64})
+    re = Matrix{Float64}(undef, w.n, length(freqs)); im = Matrix{Float64}(undef, w.n, length(freqs))
+    check(ccall((:fb_lss_freqresp, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), re, im))
+    return (; re, im)
+end
+"`Metrics(plant, build_PID(point), settings)` and `cost` (FA design/pidopt.jl:36-70) for every system of `w` and each of its m candidates, on
+its device: pid is N x m x 4 (k_p, k_i, k_d, τ_f), the plant channel (iu, iy) (1-based) of each system, weights a 5-vector (`nothing`: ones).
+The step response is RK4 with the caller's dt over round(t_sim / dt) steps, Ms the peak of the sensitivity over `freqs`. Returns metrics
+(N x m x 5: Ms, ∫e, ef, ∫u, up), cost and status (N x m; 0, FB_PID_DIVERGED = 1 or FB_PID_SINGULAR = 2: cost is infinite there)."
+function pid_metrics(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64}, t_sim::Real, dt::Real, pid::Array{Float64, 3};
+                     weights::Union{Vector{Float64}, Nothing} = nothing)
+    size(pid, 1) == w.n && size(pid, 3) == 4 || throw(DimensionMismatch("pid must be N x m x 4"))
+    m = size(pid, 2)
+    metrics = Array{Float64}(undef, w.n, m, 5); cost = Matrix{Float64}(undef, w.n, m); status = Matrix{Int32}(undef, w.n, m)
+    check(ccall((:fb_pid_metrics, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                                               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), t_sim, dt, weights === nothing ? C_NULL : weights, pid, m, metrics, cost, status))
+    return (; metrics, cost, status)
+end
 "A (N x nx x nx) and B (N x nx x nu) of the handle's own copy of the model: the matrices the device steps and designs on"
 function model(w::LinearWorld)
     a = Array{Float64}(undef, w.n, w.nx, w.nx); b = Array{Float64}(undef, w.n, w.nx, w.nu)

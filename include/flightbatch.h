@@ -367,6 +367,29 @@ enum { FB_LQR_NOT_CONVERGED = 1,   /* the iteration bound was reached (eigenvalu
        FB_LQR_NX_MAX = 16 };
 int32_t fb_lqr(fb_handle lss, const double* Q, const double* R, double* K, double* X, double* resid, int32_t* iters, int32_t* status);
 
+/* ---- the metrics of optimize_PID on a Model(lss) batch (FA design/pidopt.jl: build_PID :31-34, Metrics :36-64, cost :66-70, evaluated by
+ * optimize_PID :73-128 at every node of design/c172/c172x_design.jl, e.g. :236 for q2e; docs/design/linearize.md, "PID loop design on the
+ * device") ---------------------------------------------------------------------------------------------------------------------------
+ * The plant is channel (iu, iy) of each system of an FB_MODEL_LSS handle with 1 <= nx <= FB_PID_NX_MAX, in deviation coordinates: A,
+ * b = B[:, iu], c = C[iy, :], d = D[iy, iu] (xdot0, x0, u0, y0 play no part). Both calls read the handle's copy of the model, run on its
+ * stream and change nothing on the handle. w [nw]: 1 <= nw <= 1024 frequencies in rad/s, all positive and finite.
+ * fb_lss_freqresp: P(j w) = c inv(j w I - A) b + d (the plant of sensitivity(plant, pid), pidopt.jl:39) by complex Gauss-Jordan elimination
+ * with row pivoting; re, im [nw x N], system index fastest: element (k, i) at [k N + i]; NaN where a pivot was zero or not finite. */
+int32_t fb_lss_freqresp(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double* re, double* im);
+/* fb_pid_metrics: Metrics(plant, pid, settings) and cost (pidopt.jl:36-70) of m candidates per system, 1 <= m <= 64. pid [4 x m x N]:
+ * (k_p, k_i, k_d, tau_f) of candidate j of system i at pid[(f m + j) N + i], tau_f > 0; C(s) = k_p + k_i / s + k_d s / (tau_f s + 1)
+ * (build_PID :31-34). Unit step of the reference from rest over N_t = round(t_sim / dt) <= 200000 steps of the classical RK4 (dt > 0,
+ * t_sim >= dt), sampled at t_k = k dt. metrics [5 x m x N] (may be NULL), row order Ms, ie, ef, iu, up (Metrics :8-14): Ms = min(1e3, max over
+ * the grid of |1 / (1 + P C)|) (:39-43), ie = trapz|y - 1| / t_N, ef = |y_N - 1| (:45-52), iu = trapz|u - 1| / t_N, up = max|u - 1| (:54-60,
+ * the reference's expression). cost [m x N] = sum weights m / sum weights (:66-70); weights [5] >= 0 with a positive sum, NULL = ones.
+ * status [m x N]: 0; FB_PID_DIVERGED: a sample was not finite or beyond 1e12 (ie, ef, iu, up and cost are +Inf, Ms is the grid's);
+ * FB_PID_SINGULAR: a zero or non-finite pivot at some frequency, or 1 + d (k_p + k_d / tau_f) = 0 (the metrics are NaN, cost is +Inf).
+ * The call returns 0 in both cases. Not the reference's: its step() picks the sample time and discretises exactly, and its hinfnorm2 finds
+ * the exact peak and is infinite for an unstable loop. */
+enum { FB_PID_DIVERGED = 1, FB_PID_SINGULAR = 2, FB_PID_NX_MAX = 28 };
+int32_t fb_pid_metrics(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double t_sim, double dt, const double* weights,
+                       const double* pid, int32_t m, double* metrics, double* cost, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
