@@ -17,6 +17,7 @@ from .fleet import MixedFleet  # noqa: F401
 from .linearization import LinearizedSS, linearize, linearize_state, subsystem, delete_vars  # noqa: F401
 from .lss import LinearWorld, linear_world  # noqa: F401
 from .lqr import LqrResult, lqr, closed_loop, design_model  # noqa: F401
+from .poles import PolesResult, poles, dampreport  # noqa: F401
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)

@@ -290,6 +290,15 @@ function lqr(w::LinearWorld, q::Matrix{Float64}, r::Matrix{Float64})
                 w.handle, q, r, k, x, resid, iters, status))
     return (; k, x, resid, iters, status)
 end
+"The poles of every system of `w`, on its device (`dampreport(P)`, FA design/robot2d/robot2d_design.ipynb): the nx eigenvalues of A by balancing,
+Hessenberg reduction and double-shift QR. Returns re, im (N x nx; within a system ascending by |pole|, then Re, then Im; a pair is exact
+conjugates), iters (QR sweeps) and status (0, or FB_POLES_NOT_CONVERGED = 1 | FB_POLES_NOT_FINITE = 2: the poles are NaN there)."
+function poles(w::LinearWorld)
+    re = Matrix{Float64}(undef, w.n, w.nx); im = Matrix{Float64}(undef, w.n, w.nx)
+    iters = Vector{Int32}(undef, w.n); status = Vector{Int32}(undef, w.n)
+    check(ccall((:fb_lss_poles, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}), w.handle, re, im, iters, status))
+    return (; re, im, iters, status)
+end
 "P(jω) = c inv(jωI - A) b + d of channel (iu, iy) (1-based) of every system of `w` on the grid `freqs` (rad/s, positive), on its device: the
 plant of `sensitivity(plant, pid)` (FA design/pidopt.jl:39). Returns (re, im), each N x length(freqs)."
 function freqresp(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64})

@@ -390,6 +390,21 @@ enum { FB_PID_DIVERGED = 1, FB_PID_SINGULAR = 2, FB_PID_NX_MAX = 28 };
 int32_t fb_pid_metrics(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double t_sim, double dt, const double* weights,
                        const double* pid, int32_t m, double* metrics, double* cost, int32_t* status);
 
+/* ---- the poles of a Model(lss) batch (FA design/robot2d/robot2d_design.ipynb: `dampreport(P)` on the open loop and on the LQR velocity
+ * loop; docs/design/linearize.md, "Poles on the device") ---------------------------------------------------------------------------------
+ * For every system of an FB_MODEL_LSS handle (1 <= nx <= FB_POLES_NX_MAX, all that fb_lss_create admits): the nx eigenvalues of A by the
+ * classical dense path, eigenvalues only: balancing by powers of two without permutation, Householder reduction to Hessenberg form,
+ * double-shift QR with deflation (at most 30 sweeps per window, exceptional shifts at sweeps 10 and 20). Outputs are host arrays, any may be
+ * NULL: re, im [nx x N], system index fastest: element (k, i) at [k N + i]; iters [N] = QR sweeps taken; status [N] = 0 or FB_POLES_* bits.
+ * Within a system the poles ascend by |pole|, then Re, then Im, then the position the elimination left them in (dampreport's order by
+ * natural frequency: a function of the system's own values only); a complex pair is stored as exact conjugates, the same Re bits and
+ * +-Im. A system with a non-zero status has NaN poles; the call still returns 0. Reads A from the handle's copy of the model, runs on its
+ * stream and changes nothing on the handle. */
+enum { FB_POLES_NOT_CONVERGED = 1,   /* a window took 30 sweeps without deflating */
+       FB_POLES_NOT_FINITE = 2,      /* a non-finite entry in A (the system is not iterated on: iters = 0), or a non-finite result */
+       FB_POLES_NX_MAX = 32 };
+int32_t fb_lss_poles(fb_handle lss, double* re, double* im, int32_t* iters, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
