@@ -18,6 +18,8 @@ from .linearization import LinearizedSS, linearize, linearize_state, subsystem, 
 from .lss import LinearWorld, linear_world  # noqa: F401
 from .lqr import LqrResult, lqr, closed_loop, design_model  # noqa: F401
 from .poles import PolesResult, poles, dampreport  # noqa: F401
+from . import timeresp  # noqa: F401
+from .timeresp import StepInfo, StepResult, stepinfo  # noqa: F401  (the response itself is timeresp.step: `step` is the Simulation verb)
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)

@@ -299,6 +299,23 @@ function poles(w::LinearWorld)
     check(ccall((:fb_lss_poles, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}), w.handle, re, im, iters, status))
     return (; re, im, iters, status)
 end
+"`stepinfo(step(P[:y, :u], t_sim))` (FA design/robot2d/robot2d_design.ipynb) of the channels `channels` = [(iu, iy), ...] (1-based) of every system of
+`w`, on its device: the unit step response from rest by the classical RK4 at the caller's `dt`, sampled at k dt. Returns y0, yf, stepsize, peak,
+peaktime, overshoot, undershoot, settlingtime, risetime (each N x m) and status (0, or FB_STEPINFO_DIVERGED = 1: every field NaN,
+FB_STEPINFO_FLAT = 2: the ratios and times NaN). `y0`, `yf`: N x m matrices whose NaN entries mean the first / last sample, or `nothing`."
+function stepinfo(w::LinearWorld, channels, t_sim::Real; dt::Real, y0=nothing, yf=nothing, settling_th::Real=0.02, risetime_th=(0.1, 0.9))
+    m = length(channels)
+    iu = Int32[c[1] - 1 for c in channels]; iy = Int32[c[2] - 1 for c in channels]
+    opts = Float64[settling_th, risetime_th[1], risetime_th[2]]
+    info = Array{Float64}(undef, w.n, m, 9); status = Matrix{Int32}(undef, w.n, m)
+    p0 = y0 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(y0); pf = yf === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yf)
+    Base.GC.@preserve y0 yf check(ccall((:fb_lss_stepinfo, lib), Cint,
+          (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int32, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+          w.handle, iu, iy, m, t_sim, dt, opts, p0, pf, 1, Ptr{Cdouble}(C_NULL), info, status))
+    f = k -> info[:, :, k]
+    return (; y0 = f(1), yf = f(2), stepsize = f(3), peak = f(4), peaktime = f(5), overshoot = f(6), undershoot = f(7), settlingtime = f(8),
+            risetime = f(9), status)
+end
 "P(jω) = c inv(jωI - A) b + d of channel (iu, iy) (1-based) of every system of `w` on the grid `freqs` (rad/s, positive), on its device: the
 plant of `sensitivity(plant, pid)` (FA design/pidopt.jl:39). Returns (re, im), each N x length(freqs)."
 function freqresp(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64})

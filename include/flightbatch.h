@@ -405,6 +405,30 @@ enum { FB_POLES_NOT_CONVERGED = 1,   /* a window took 30 sweeps without deflatin
        FB_POLES_NX_MAX = 32 };
 int32_t fb_lss_poles(fb_handle lss, double* re, double* im, int32_t* iters, int32_t* status);
 
+/* ---- step responses and StepInfo of a Model(lss) batch (FA design/robot2d/robot2d_design.ipynb: `step(P[:y, :u], t_sim)` and `stepinfo` of
+ * it on the velocity loop and on the position loop; docs/design/linearize.md, "Step responses on the device") -------------------------------
+ * For m channels (iu[j], iy[j]), 1 <= m <= 64, of every system of an FB_MODEL_LSS handle with 1 <= nx <= FB_STEPINFO_NX_MAX: the unit step
+ * response of x' = A x + b, y = c x + d (b = B[:, iu], c = C[iy, :], d = D[iy, iu]; xdot0, x0, u0, y0 play no part) from rest, sampled at
+ * t_k = k dt, k = 0 .. N_t, N_t = round(t_sim / dt) <= 200000, by the classical RK4 (dt > 0, t_sim >= dt). Pair (j, i) of channel j and
+ * system i is stored at [j N + i], the system index fastest.
+ * opts: NULL or {settling_th, rise_lo, rise_hi} (NULL = 0.02, 0.1, 0.9; settling_th > 0, 0 < rise_lo < rise_hi < 1).
+ * y0_in, yf_in: NULL or [m x N], the initial and final value stepinfo measures from; a NaN entry (and NULL) means the first / last sample.
+ * y: NULL or [ns x m x N], ns = fb_lss_stepinfo_samples(N_t, stride) = ceil(N_t / stride) + 1: sample s stride at row s, and sample N_t at
+ * the last row whether stride divides N_t or not (stride >= 1).
+ * info [9 x m x N], row order y0, yf, stepsize, peak, peaktime, overshoot, undershoot, settlingtime, risetime: stepsize = |yf - y0|,
+ * dir = sign(yf - y0); peak = max y (dir > 0) or min y (dir < 0) at its first index, peaktime that index times dt; overshoot =
+ * dir 100 (peak - yf) / stepsize; undershoot = 100 (y0 - min y) / stepsize for dir > 0, 100 (max y - y0) / stepsize for dir < 0, not below 0;
+ * settlingtime = t one sample past the last sample with |y - yf| > settling_th stepsize, at most t_N, 0 if there is none; risetime =
+ * t[first k with dir (y_k - y0) > rise_hi stepsize] - t[first k with dir (y_k - y0) > rise_lo stepsize], NaN if either is never reached.
+ * status [m x N]: 0; FB_STEPINFO_DIVERGED: a sample was not finite or beyond 1e12 (every info row is NaN); FB_STEPINFO_FLAT: stepsize is 0
+ * or not finite (y0, yf, stepsize, peak and peaktime as defined with dir = +1; the four ratios and times are NaN). The call returns 0 in both
+ * cases. Reads the handle's copy of the model, runs on its stream and changes nothing on the handle. Not the reference's: its step() picks
+ * the sample time and discretises exactly. */
+enum { FB_STEPINFO_DIVERGED = 1, FB_STEPINFO_FLAT = 2, FB_STEPINFO_NX_MAX = 31 };
+int32_t fb_lss_stepinfo_samples(int32_t nsteps, int32_t stride);   /* -1 unless nsteps >= 1 and stride >= 1 */
+int32_t fb_lss_stepinfo(fb_handle lss, const int32_t* iu, const int32_t* iy, int32_t m, double t_sim, double dt, const double* opts,
+                        const double* y0_in, const double* yf_in, int32_t stride, double* y, double* info, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
