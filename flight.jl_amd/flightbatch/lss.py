@@ -99,6 +99,12 @@ class LinearWorld(BatchedWorld):
         check(lib.fb_lss_get_model(self._h, _pd(A), _pd(B)))
         return unpack_matrix(A, self.nx, self.nx), unpack_matrix(B, self.nx, self.nu)
 
+    def model_cd(self):
+        """(C [n, ny, nx], D [n, ny, nu]): the output half of the handle's own copy of the model (read-only)"""
+        Cm, D = np.empty(self.ny * self.nx * self.n), np.empty(self.ny * self.nu * self.n)
+        check(lib.fb_lss_get_cd(self._h, _pd(Cm), _pd(D)))
+        return unpack_matrix(Cm, self.ny, self.nx), unpack_matrix(D, self.ny, self.nu)
+
     @property
     def exchange(self) -> str:
         """"panel" or "shfl": how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"""

@@ -344,6 +344,28 @@ function model(w::LinearWorld)
     check(ccall((:fb_lss_get_model, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), w.handle, a, b))
     return (; a, b)
 end
+"C (N x ny x nx) and D (N x ny x nu) of the handle's own copy of the model: the companion of `model`"
+function model_cd(w::LinearWorld)
+    c = Array{Float64}(undef, w.n, w.ny, w.nx); d = Array{Float64}(undef, w.n, w.ny, w.nu)
+    check(ccall((:fb_lss_get_cd, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), w.handle, c, d))
+    return (; c, d)
+end
+"`connect` / `series` / `feedback` (FA design/c172/c172x_design.jl:199-216, 226-227, 244-263) on the device: with v = [u_p; u_c] and z = [y_p; y_c]
+the interconnection v = feedback z[reads] + inputs w closed around `p` and `c` (`nothing`: no compensator). `feedback` is nv x nf for the batch or
+N x nv x nf per system, `inputs` nv x nw or N x nv x nw; `reads`, `outputs`: 1-based rows of z (`outputs = nothing`: every row). Returns the new
+`LinearWorld` (states [x_p; x_c], inputs w, outputs z[outputs], at rest) and status (0, FB_CONNECT_ILL_POSED = 1 or FB_CONNECT_NOT_FINITE = 2:
+that system's matrices are NaN)."
+function connect(p::LinearWorld, c::Union{LinearWorld, Nothing} = nothing; feedback::Array{Float64}, inputs::Array{Float64}, reads, outputs = nothing)
+    jz = Int32.(reads .- 1); iz = outputs === nothing ? Int32[] : Int32.(outputs .- 1)
+    nw = size(inputs, ndims(inputs))
+    status = Vector{Int32}(undef, p.n)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_connect, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Int32},
+                                               Int32, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                p.handle, c === nothing ? C_NULL : c.handle, jz, length(jz), feedback, ndims(feedback) == 3 ? 1 : 0, inputs, ndims(inputs) == 3 ? 1 : 0, nw,
+                outputs === nothing ? C_NULL : iz, length(iz), status, h))
+    return (; world = LinearWorld(h[]), status)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

@@ -429,6 +429,31 @@ int32_t fb_lss_stepinfo_samples(int32_t nsteps, int32_t stride);   /* -1 unless 
 int32_t fb_lss_stepinfo(fb_handle lss, const int32_t* iu, const int32_t* iy, int32_t m, double t_sim, double dt, const double* opts,
                         const double* y0_in, const double* yf_in, int32_t stride, double* y, double* info, int32_t* status);
 
+/* ---- connect / series / feedback on Model(lss) batches (FA design/c172/c172x_design.jl:199-216, 226-227, 244-263, ...: the `connect`,
+ * `series` and `feedback` calls between the design verbs; docs/design/linearize.md, "Closing loops on the device") --------------------------
+ * The plant p (nx_p, nu_p, ny_p) and the optional compensator c (nx_c, nu_c, ny_c; NULL: none), two FB_MODEL_LSS handles with the same N on
+ * one device, are connected through static gains into a new FB_MODEL_LSS handle, system by system, in deviation coordinates (the offsets
+ * xdot0, x0, u0, y0 play no part, as named_ss(lss) drops them). With v = [u_p; u_c] (nv rows), z = [y_p; y_c] (nz rows), x = [x_p; x_c] and
+ * the block-diagonal stacked model x' = A x + B v, z = C x + D v:
+ *     v = F z[jz] + G w           jz [nf]: the rows of z the feedback reads; F [nv x nf]; w: the nw inputs of the new model; G [nv x nw]
+ *     E = inv(I - F D[jz, :]), M = E F C[jz, :], Nw = E G
+ *     A' = A + B M,  B' = B Nw,  C' = C[iz, :] + D[iz, :] M,  D' = D[iz, :] Nw          iz [ny]: the rows of z the new model outputs
+ * F and G are host arrays, column-major: one matrix for the batch (*_per_system = 0) or one per system in fb_linearize's layout, element
+ * (i, r, col) at [(r + rows col) N + i] (K of fb_lqr is in that layout). iz = NULL means every row of z (nz <= 64). status [N] may be NULL:
+ * 0; FB_CONNECT_NOT_FINITE: a non-finite entry in the source models, in F or in G; otherwise FB_CONNECT_ILL_POSED: a zero or non-finite
+ * pivot of I - F D[jz, :] (Gauss-Jordan elimination, the pivot of a step the largest magnitude among the rows not yet used). Such a system
+ * gets A', B', C', D' all NaN; the call still returns 0 and no other system changes in any bit.
+ * The new handle: on p's device, with p's dt and p's stream rule (fb_lss_from_linearization), at x = 0, u = 0, t = 0, xdot0 = x0 = u0 = y0 =
+ * 0; every verb of an FB_MODEL_LSS handle works on it. p and c are only read. Refused, with nothing launched and no handle created: a NULL or
+ * non-LSS p, a non-LSS c, a handle without a model, c on another device or with another N, nx_p + nx_c > 32, nv > FB_CONNECT_NV_MAX,
+ * nz > FB_CONNECT_NZ_MAX, nf outside 1 .. FB_CONNECT_NF_MAX, nw outside 1 .. 8, ny outside 1 .. 64, an index of jz or iz outside [0, nz),
+ * NULL F, G, jz or out. */
+enum { FB_CONNECT_ILL_POSED = 1, FB_CONNECT_NOT_FINITE = 2, FB_CONNECT_NV_MAX = 16, FB_CONNECT_NF_MAX = 32, FB_CONNECT_NZ_MAX = 128 };
+int32_t fb_lss_connect(fb_handle p, fb_handle c /* NULL: no compensator */, const int32_t* jz, int32_t nf, const double* F, int32_t f_per_system,
+                       const double* G, int32_t g_per_system, int32_t nw, const int32_t* iz, int32_t ny, int32_t* status, fb_handle* out);
+/* The companion of fb_lss_get_model: C [ny x nx x N] and D [ny x nu x N] of the handle's own copy, in fb_linearize's layout (either may be NULL). */
+int32_t fb_lss_get_cd(fb_handle h, double* C, double* D);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
