@@ -6,7 +6,7 @@
 //   E = inv(I - F D[jz, :]), M = E F C[jz, :], Nw = E G;  A' = A + B M, B' = B Nw, C' = C[iz, :] + D[iz, :] M, D' = D[iz, :] Nw.
 // One system per group of P lanes of one wave (P = 8, 16 or 32, the smallest >= max(nx_p + nx_c, nv); 64 / P systems per wave, one wave per
 // workgroup). Lane r < nv owns row r of [I - F D_jz | F C_jz | G] as three register arrays; Gauss-Jordan elimination on the augmented rows with
-// the family's pivot rule (lqr_kernels.hpp: the group-wide maximum over the rows not yet used, then the lowest lane that holds it), every step a
+// the family's pivot rule (fbg::Lanes::pivot, lss_group.hpp), every step a
 // compile-time k, the steps k >= nv behind a wave-uniform branch. The rows stay with their lanes: the lane that was the pivot of step k ends
 // with row k of [M | Nw] and puts it at row k of the group's LDS panel. Lane r < nx then forms row r of [A' | B'], and every lane the output
 // rows r, r + P, ... of [C' | D'], reading [M | Nw] back as broadcasts. The blocks of the stacked model that are zero by construction are
@@ -14,20 +14,18 @@
 // The panel belongs to one wave: fences and wave_barrier, no s_barrier. Lanes past the batch's end work on the last system again and store
 // nothing. The result goes to a staging block in fb_linearize's layout; fbl::k_lss_gather makes the new handle's copy from it.
 #pragma once
-#include "lss_kernels.hpp"
-#include "lqr_kernels.hpp"
+#include "lss_group.hpp"
+#include "../../include/flightbatch.h"
 
 namespace fbc {
 
-using fbq::Group;
-using fbq::is_fin;
-using fbq::panel_sync;
+using namespace fbg;
 
-constexpr int CN_WAVE = 64;
+constexpr int CN_WAVE = fbg::WAVE;
 constexpr int CN_NW_MAX = 8;      // the inputs of the new model: fbl::LSS_NU_MAX
 
 struct ConnectSide {
-    const double* ab; const double* cd;   // a handle's copies (lss_kernels.hpp), G its group size
+    const double* ab; const double* cd;   // a handle's copies (fbg::ab_index, lss_group.hpp), G its group size
     int nx, nu, ny, G;
 };
 struct ConnectArgs {
@@ -47,11 +45,11 @@ __device__ inline bool side_finite(const ConnectSide& s, int64_t n, int64_t i, i
     bool fin = true;
     const int64_t S = n * s.G, slot0 = i * s.G;
     if (r < s.nx) {
-        for (int c = 0; c < s.nx; c++) fin = fin && is_fin(s.ab[(int64_t)c * S + slot0 + r]);
-        for (int c = 0; c < s.nu; c++) fin = fin && is_fin(s.ab[(int64_t)(s.G + c) * S + slot0 + r]);
+        for (int c = 0; c < s.nx; c++) fin = fin && is_fin(s.ab[ab_index(S, slot0, c) + r]);
+        for (int c = 0; c < s.nu; c++) fin = fin && is_fin(s.ab[ab_index(S, slot0, s.G + c) + r]);
     }
     for (int c = 0; c < s.nx + s.nu; c++)
-        for (int j = r; j < s.ny; j += P) fin = fin && is_fin(s.cd[((int64_t)c * n + i) * s.ny + j]);
+        for (int j = r; j < s.ny; j += P) fin = fin && is_fin(s.cd[cd_index(n, i, s.ny, j, c)]);
     return fin;
 }
 
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
     constexpr int NVP = P < FB_CONNECT_NV_MAX ? P : FB_CONNECT_NV_MAX, NW = CN_NW_MAX;
     constexpr int ROW = NVP + P + NW, LD = P + NW + 1, NG = CN_WAVE / P, GRP = ROW + NVP * LD;   // (ROW and GRP are even: 16-byte rows)
     __shared__ __attribute__((aligned(16))) double lds[NG * GRP];
-    const Group<P> g(lds, nullptr);   // (for the group's lane index, maximum and ballot only: its panels are never touched here)
+    const fbg::Lanes<P> g;
     double* prow = lds + (threadIdx.x / P) * GRP;   // the scaled pivot row of the current step: e | m | gw
     double* sol = prow + ROW;                       // [M | Nw], NVP x LD
     const int r = g.r;
@@ -71,7 +69,8 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
     const bool valid = i_own < n;
     const int64_t i = valid ? i_own : n - 1;
     const int64_t Sp = n * a.p.G, slotp = i * a.p.G, Sc = n * a.c.G, slotc = i * a.c.G;
-    const double* cdp = a.p.cd + i * nyp;           // element (z, col) of the plant's [C | D] at cdp[col n ny_p + z]
+    // cd_index at unrolled columns, base and column pitch hoisted by hand (58 to 185 registers fewer): (z, col) at cdp[col cpitch + z]
+    const double* cdp = a.p.cd + i * nyp;
     const double* cdc = a.c.cd + i * a.c.ny;
     const int64_t cpitch = n * nyp, ccpitch = n * a.c.ny;
 
@@ -125,13 +124,10 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
 #pragma unroll
     for (int k = 0; k < NVP; k++) {
         if (k < nv) {
-            const double v = used ? -1.0 : fabs(e[k]);
-            const double mx = g.gmax(v);
-            const unsigned cand = g.mask(!used && v == mx);
-            ok = ok && cand != 0 && mx > 0.0 && is_fin(mx);
-            const int p = cand ? __builtin_ctz(cand) : k;
+            const fbg::Pivot pv = g.pivot(used, used ? -1.0 : fabs(e[k]), k);
+            ok = ok && pv.found;
             panel_sync();
-            if (r == p) {
+            if (r == pv.p) {
                 const double ip = 1.0 / e[k];
 #pragma unroll
                 for (int j = k + 1; j < NVP; j++) { e[j] *= ip; prow[j] = e[j]; }
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
                 used = true; myk = k;
             }
             panel_sync();
-            if (live && r != p) {
+            if (live && r != pv.p) {
                 const double f = e[k];
 #pragma unroll
                 for (int j = k + 1; j < NVP; j++) e[j] = fma(-f, prow[j], e[j]);
@@ -186,15 +182,15 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
 #pragma unroll
         for (int c = 0; c < P; c++) {
             double v = 0.0;
-            if (inp) { if (c < nxp) v = a.p.ab[(int64_t)c * Sp + slotp + r]; }
-            else if (c >= nxp && c < nx) v = a.c.ab[(int64_t)(c - nxp) * Sc + slotc + rc];
+            if (inp) { if (c < nxp) v = a.p.ab[ab_index(Sp, slotp, c) + r]; }
+            else if (c >= nxp && c < nx) v = a.c.ab[ab_index(Sc, slotc, c - nxp) + rc];
             ar[c] = v;
         }
 #pragma unroll
         for (int c = 0; c < NW; c++) br[c] = 0.0;
         const int k0 = inp ? 0 : nup, k1 = inp ? nup : nv;
         for (int k = k0; k < k1; k++) {
-            const double b = inp ? a.p.ab[(int64_t)(a.p.G + k) * Sp + slotp + r] : a.c.ab[(int64_t)(a.c.G + k - nup) * Sc + slotc + rc];
+            const double b = inp ? a.p.ab[ab_index(Sp, slotp, a.p.G + k) + r] : a.c.ab[ab_index(Sc, slotc, a.c.G + k - nup) + rc];
             const double* s = sol + k * LD;
 #pragma unroll
             for (int c = 0; c < P; c++) ar[c] = fma(b, s[c], ar[c]);

@@ -14,6 +14,7 @@
 #include "robot2d_kernels.hpp"
 #include "scenario_kernels.hpp"
 #include "lin_kernels.hpp"
+#include "lss_group.hpp"
 #include "lss_kernels.hpp"
 #include "lqr_kernels.hpp"
 #include "pid_kernels.hpp"
@@ -982,10 +983,7 @@ static int32_t step_raw(fb_handle h, int64_t nsteps) {
         const int k = (int)(left < h->steps_per_launch ? left : h->steps_per_launch);
         a.ctl_phase = a.ctl_ratio > 0 ? (int)(h->steps_done % a.ctl_ratio) : 0;
         a.step0 = h->steps_done;
-        const bool stamp = h->timing && h->lev_used < h->lev_max;
-        if (stamp) HIPCHK(hipEventRecord(h->lev[2 * h->lev_used], h->stream));
-        launch_step(h, grid_for(h->n, 256), a, k);
-        if (stamp) { HIPCHK(hipEventRecord(h->lev[2 * h->lev_used + 1], h->stream)); h->lev_used++; }
+        if (int32_t rc = stamped(h, [&] { launch_step(h, grid_for(h->n, 256), a, k); })) return rc;   // (fb_lss.inc)
         left -= k;
         h->steps_done += k;
         h->launches++;

@@ -1,32 +1,14 @@
 // fb_connect.inc — connect / series / feedback on Model(lss) batches (include/flightbatch.h: fb_lss_connect, fb_lss_get_cd; kernels:
-// connect_kernels.hpp; docs/design/linearize.md, "Closing loops on the device"). Included by fb_capi.hip after fb_lss.inc.
+// connect_kernels.hpp; docs/design/linearize.md, "Closing loops on the device"). Included by fb_capi.hip after fb_lss.inc (the verbs' shared scaffold).
 // Reference: the `connect`, `series` and `feedback` calls between the design verbs of FA design/c172/c172x_design.jl:199-216, 226-227, 244-263,
 // 287-292, 317-322, 395-425, 601-617, 724-727, 754-757, and the `connect` cells of design/robot2d/robot2d_design.ipynb.
 // Every refusal is decided here, before anything is launched or created. The kernel runs on the plant's stream (where fb_timing_begin_per_launch
 // on the plant stamps it); the new handle's copy of the model is then written by k_lss_gather with the identity lists, like every other.
 
-static int connect_group(int nx, int nv) { const int m = nx > nv ? nx : nv; return m <= 8 ? 8 : m <= 16 ? 16 : 32; }
-
 extern "C" {
 
 int32_t fb_lss_get_cd(fb_handle h, double* C, double* D) {
-    if (!h) return fail("null handle");
-    if (!is_lss(h)) return fail("fb_lss_get_cd: the handle is not a LinearizedSS handle (fb_lss_create)");
-    if (int32_t rc = lss_ready(h)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const LssState* L = h->lss;
-    const int64_t n = h->n, nx = L->nx, nu = L->nu, ny = L->ny;
-    std::vector<double> cd((size_t)((nx + nu) * ny * n));   // the kernels' copy: (j, c) of system i at [(c n + i) ny + j]
-    HIPCHK(hipMemcpyAsync(cd.data(), L->cd, sizeof(double) * cd.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int64_t c = 0; c < nx + nu; c++) {
-        double* out = c < nx ? C : D;
-        if (!out) continue;
-        const int64_t oc = c < nx ? c : c - nx;
-        for (int64_t j = 0; j < ny; j++)
-            for (int64_t i = 0; i < n; i++) out[(j + ny * oc) * n + i] = cd[(c * n + i) * ny + j];
-    }
-    return 0;
+    return lss_unpad("fb_lss_get_cd", h, true, C, D, [](const LssState* L, int64_t n, int64_t i, int r, int c) { return fbg::cd_index(n, i, L->ny, r, c); });
 }
 
 int32_t fb_lss_connect(fb_handle p, fb_handle c, const int32_t* jz, int32_t nf, const double* F, int32_t f_per_system,
@@ -67,52 +49,38 @@ int32_t fb_lss_connect(fb_handle p, fb_handle c, const int32_t* jz, int32_t nf, 
     const size_t szAB = (size_t)nx * nc * un, szCD = (size_t)ny * nc * un, szZ = (size_t)nzero * un;
     std::vector<int32_t> idx(jz, jz + nf);
     for (int k = 0; k < ny; k++) idx.push_back(iz ? iz[k] : k);
+    NewHandle made;   // (destroyed on every failing path below, after the blocks are freed)
+    DevBlocks blocks;
     double* d = nullptr;
     int32_t* di = nullptr;
-    fb_handle h = nullptr;
-    auto run = [&]() -> int32_t {
-        if (c) HIPCHK(hipStreamSynchronize(c->stream));   // (the compensator's model, should its stream still be writing it)
-        HIPCHK(hipMalloc(&d, sizeof(double) * (szF + szG + szAB + szCD + szZ)));
-        HIPCHK(hipMalloc(&di, sizeof(int32_t) * (idx.size() + un)));
-        if (int32_t rc = lss_new_handle(nx, nw, ny, n, p->device, &h)) return rc;
-        double *dF = d, *dG = dF + szF, *dAB = dG + szG, *dCD = dAB + szAB, *dZ = dCD + szCD;
-        HIPCHK(hipMemcpyAsync(dF, F, sizeof(double) * szF, hipMemcpyHostToDevice, p->stream));
-        HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * szG, hipMemcpyHostToDevice, p->stream));
-        HIPCHK(hipMemcpyAsync(di, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, p->stream));
-        HIPCHK(hipMemsetAsync(dZ, 0, sizeof(double) * szZ, p->stream));
-        fbc::ConnectArgs a = {};
-        a.p = {Lp->ab, Lp->cd, nxp, nup, nyp, Lp->G};
-        if (c) a.c = {Lc->ab, Lc->cd, nxc, nuc, nyc, Lc->G};
-        a.jz = di; a.iz = di + nf;
-        a.F = dF; a.f_e = f_per_system ? n : 1; a.f_s = f_per_system ? 1 : 0;
-        a.G = dG; a.g_e = g_per_system ? n : 1; a.g_s = g_per_system ? 1 : 0;
-        a.AB = dAB; a.CD = dCD; a.status = di + idx.size();
-        a.n = n; a.nf = nf; a.nw = nw; a.ny = ny;
-        const int P = connect_group(nx, nv);
-        const dim3 grid = grid_for(n, fbc::CN_WAVE / P), block(fbc::CN_WAVE);
-        const bool stamp = p->timing && p->lev_used < p->lev_max;
-        if (stamp) HIPCHK(hipEventRecord(p->lev[2 * p->lev_used], p->stream));
-        if (P == 8) hipLaunchKernelGGL(fbc::k_connect<8>, grid, block, 0, p->stream, a);
-        else if (P == 16) hipLaunchKernelGGL(fbc::k_connect<16>, grid, block, 0, p->stream, a);
-        else hipLaunchKernelGGL(fbc::k_connect<32>, grid, block, 0, p->stream, a);
-        if (stamp) { HIPCHK(hipEventRecord(p->lev[2 * p->lev_used + 1], p->stream)); p->lev_used++; }
-        HIPCHK(hipGetLastError());
-        if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(hipStreamSynchronize(p->stream));   // (the staging block the new handle's stream is about to read)
-        fbl::LssSrc s;
-        s.xdot0 = s.x0 = s.u0 = s.y0 = dZ;          // deviation coordinates: every offset is zero
-        s.AB = dAB; s.CD = dCD; s.snx = nx; s.snu = nw; s.sny = ny; s.idx = nullptr;
-        if (int32_t rc = lss_gather(h, s, nullptr, nullptr, nullptr)) return rc;
-        h->params.dt = p->params.dt;
-        if (p->stream != p->own_stream) h->stream = p->stream;   // (fb_lss_from_linearization's rule)
-        return 0;
-    };
-    const int32_t rc = run();
-    const std::string msg = g_err;
-    (void)hipFree(d); (void)hipFree(di);
-    if (rc) { if (h) fb_destroy(h); g_err = msg; return rc; }
-    g_err = msg;
-    *out = h;
+    if (c) HIPCHK(hipStreamSynchronize(c->stream));   // (the compensator's model, should its stream still be writing it)
+    if (int32_t rc = blocks.alloc(&d, szF + szG + szAB + szCD + szZ)) return rc;
+    if (int32_t rc = blocks.alloc(&di, idx.size() + un)) return rc;
+    if (int32_t rc = lss_new_handle(nx, nw, ny, n, p->device, &made.h)) return rc;
+    const fb_handle h = made.h;
+    double *dF = d, *dG = dF + szF, *dAB = dG + szG, *dCD = dAB + szAB, *dZ = dCD + szCD;
+    HIPCHK(hipMemcpyAsync(dF, F, sizeof(double) * szF, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * szG, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(di, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemsetAsync(dZ, 0, sizeof(double) * szZ, p->stream));
+    fbc::ConnectArgs a = {};
+    a.p = {Lp->ab, Lp->cd, nxp, nup, nyp, Lp->G};
+    if (c) a.c = {Lc->ab, Lc->cd, nxc, nuc, nyc, Lc->G};
+    a.jz = di; a.iz = di + nf;
+    a.F = dF; a.f_e = f_per_system ? n : 1; a.f_s = f_per_system ? 1 : 0;
+    a.G = dG; a.g_e = g_per_system ? n : 1; a.g_s = g_per_system ? 1 : 0;
+    a.AB = dAB; a.CD = dCD; a.status = di + idx.size();
+    a.n = n; a.nf = nf; a.nw = nw; a.ny = ny;
+    if (int32_t rc = family_launch(p, group_for(nx > nv ? nx : nv), n, a, [](auto P) { return fbc::k_connect<P.value>; })) return rc;
+    if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));   // (the staging block the new handle's stream is about to read)
+    fbl::LssSrc s;
+    s.xdot0 = s.x0 = s.u0 = s.y0 = dZ;          // deviation coordinates: every offset is zero
+    s.AB = dAB; s.CD = dCD; s.snx = nx; s.snu = nw; s.sny = ny; s.idx = nullptr;
+    if (int32_t rc = lss_gather(h, s, nullptr, nullptr, nullptr)) return rc;
+    h->params.dt = p->params.dt;
+    if (p->stream != p->own_stream) h->stream = p->stream;   // (fb_lss_from_linearization's rule)
+    *out = made.release();
     return 0;
 }
 

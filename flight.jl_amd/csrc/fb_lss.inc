@@ -3,7 +3,8 @@
 // Reference: FP/linearization.jl:157-192 — a LinearizedSS is a ModelDefinition with X = copy(x0), U = copy(u0), @no_step, @no_periodic
 // and f_ode!: xdot = xdot0 + A (x - x0) + B (u - u0), y = y0 + C (x - x0) + D (u - u0).
 // The state, input, output and derivative rows are the handle's x, u, y, xdot in the ABI's layout [rows x n], so that the state copies and the
-// device log work on them as on any other model; the model itself is the handle's own copy in the stepper's layout (lss_kernels.hpp).
+// device log work on them as on any other model; the model itself is the handle's own copy in the layout stated at fbg::ab_index (lss_group.hpp).
+// First comes what every verb of the family shares on the host (docs/design/linearize.md, "What the family shares").
 
 struct LssState {
     int nx = 0, nu = 0, ny = 0, G = 0;
@@ -19,7 +20,58 @@ static bool is_lss(fb_handle h) { return h->model == FB_MODEL_LSS; }
 static int32_t lss_refuse(const char* verb, const char* why) {
     return fail("%s: not defined for a LinearizedSS handle (FB_MODEL_LSS): %s", verb, why);
 }
-static int lss_group(int nx) { return nx <= 4 ? 4 : nx <= 8 ? 8 : nx <= 16 ? 16 : 32; }
+// the group size of the verbs with 8 / 16 / 32 instances: the smallest with a lane per row (the stepper's own has 4 as well)
+static int group_for(int rows) { return rows <= 8 ? 8 : rows <= 16 ? 16 : 32; }
+static int lss_group(int nx) { return nx <= 4 ? 4 : group_for(nx); }
+
+// `launch` between a pair of per-launch timing stamps of h, when those are on and the window has room (fb_timing_begin_per_launch)
+template <class F>
+static int32_t stamped(fb_handle h, F&& launch) {
+    const bool stamp = h->timing && h->lev_used < h->lev_max;
+    if (stamp) HIPCHK(hipEventRecord(h->lev[2 * h->lev_used], h->stream));
+    launch();
+    if (stamp) { HIPCHK(hipEventRecord(h->lev[2 * h->lev_used + 1], h->stream)); h->lev_used++; }
+    return 0;
+}
+// a verb's kernel on h's stream, stamped: `groups` groups of P lanes, 64 / P to a one-wave workgroup; kernel(P) = [](auto P) { return k<P.value>; }
+template <class Args, class K>
+static int32_t family_launch(fb_handle h, int P, int64_t groups, const Args& a, K&& kernel) {
+    using std::integral_constant;
+    void (*const k)(Args) = P == 8 ? kernel(integral_constant<int, 8>{}) : P == 16 ? kernel(integral_constant<int, 16>{}) : kernel(integral_constant<int, 32>{});
+    const dim3 grid = grid_for(groups, fbg::WAVE / P), block(fbg::WAVE);
+    if (int32_t rc = stamped(h, [&] { hipLaunchKernelGGL(k, grid, block, 0, h->stream, a); })) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the device blocks of one call: freed when the call returns, on every path; g_err stays as the step that failed left it
+struct DevBlocks {
+    std::vector<void*> held;
+    ~DevBlocks() { for (void* p : held) (void)hipFree(p); }
+    template <class T> int32_t alloc(T** out, size_t count) { HIPCHK(hipMalloc(out, sizeof(T) * count)); held.push_back(*out); return 0; }
+};
+// a handle in the making: destroyed when the call returns, with the failing step's reason kept, unless it was handed over
+struct NewHandle {
+    fb_handle h = nullptr;
+    ~NewHandle() { if (h) { const std::string msg = g_err; fb_destroy(h); g_err = msg; } }
+    fb_handle release() { fb_handle r = h; h = nullptr; return r; }
+};
+
+// what a design verb asks of its handle, in this order; then, where the verb's own order of checks puts it, that it has a model
+static int32_t verb_handle(const char* verb, fb_handle h, int nx_max, const char* takes, const char* limit) {
+    if (!h) return fail("null handle");
+    if (!is_lss(h)) return fail("%s: the handle is not a LinearizedSS handle (FB_MODEL_LSS: fb_lss_create, fb_lss_from_linearization)", verb);
+    const LssState* L = h->lss;
+    if (!L) return fail("%s: the handle is not ready (its creation did not finish)", verb);
+    if (L->nx < 1 || L->nx > nx_max) return fail("%s: nx = %d, the %s takes 1 <= nx <= %d (%s)", verb, L->nx, takes, nx_max, limit);
+    return 0;
+}
+static int32_t verb_model(const char* verb, fb_handle h) {
+    return h->lss->have_model ? 0 : fail("%s: this LinearizedSS handle has no model yet (fb_lss_set_model)", verb);
+}
+// the model's fields of a verb's argument struct from the handle: [A | B] with its sizes; for a verb on a channel also [C | D], nu and ny
+template <class A> static void verb_args_ab(A& a, fb_handle h) { a.ab = h->lss->ab; a.n = h->n; a.nx = h->lss->nx; a.G = h->lss->G; }
+template <class A> static void verb_args(A& a, fb_handle h) { verb_args_ab(a, h); a.cd = h->lss->cd; a.nu = h->lss->nu; a.ny = h->lss->ny; }
 static int lss_exchange() { const char* e = getenv("FLIGHTBATCH_LSS_EXCHANGE"); return e && !strcmp(e, "shfl") ? 1 : 0; }
 
 static fbl::LssArgs lss_args(fb_handle h) {
@@ -101,13 +153,13 @@ static int32_t lss_step(fb_handle h, int64_t nsteps) {
     int64_t left = nsteps;
     while (left > 0) {
         const int k = (int)(left < h->steps_per_launch ? left : h->steps_per_launch);
-        const bool stamp = h->timing && h->lev_used < h->lev_max;
-        if (stamp) HIPCHK(hipEventRecord(h->lev[2 * h->lev_used], h->stream));
-        lss_with_group(L, [&](auto G) {
-            if (L->xch == 0) hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 0>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
-            else hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 1>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+        const int32_t rc = stamped(h, [&] {
+            lss_with_group(L, [&](auto G) {
+                if (L->xch == 0) hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 0>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+                else hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 1>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+            });
         });
-        if (stamp) { HIPCHK(hipEventRecord(h->lev[2 * h->lev_used + 1], h->stream)); h->lev_used++; }
+        if (rc) return rc;
         left -= k;
         h->steps_done += k;
         h->launches++;
@@ -124,24 +176,39 @@ static int32_t lss_gather(fb_handle h, fbl::LssSrc s, const int32_t* ix, const i
     for (int k = 0; k < L->nx; k++) idx.push_back(ix ? ix[k] : k);
     for (int k = 0; k < L->nu; k++) idx.push_back(iu ? iu[k] : k);
     for (int k = 0; k < L->ny; k++) idx.push_back(iy ? iy[k] : k);
+    DevBlocks blocks;
     int32_t* d_idx = nullptr;
-    HIPCHK(hipMalloc(&d_idx, sizeof(int32_t) * idx.size()));
-    int32_t rc = 0;
-    auto run = [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, h->stream));
-        s.idx = d_idx;
-        const fbl::LssDst d = {L->ab, L->xs, L->u0, L->y0, L->cd, h->x, h->u, L->nx, L->nu, L->ny, L->G, h->n};
-        hipLaunchKernelGGL(fbl::k_lss_gather, grid_for(h->n, fbl::LSS_BLOCK), dim3(fbl::LSS_BLOCK), 0, h->stream, s, d);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return 0;
-    };
-    rc = run();
-    (void)hipFree(d_idx);
-    if (rc) return rc;
+    if (int32_t rc = blocks.alloc(&d_idx, idx.size())) return rc;
+    HIPCHK(hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, h->stream));
+    s.idx = d_idx;
+    const fbl::LssDst d = {L->ab, L->xs, L->u0, L->y0, L->cd, h->x, h->u, L->nx, L->nu, L->ny, L->G, h->n};
+    hipLaunchKernelGGL(fbl::k_lss_gather, grid_for(h->n, fbl::LSS_BLOCK), dim3(fbl::LSS_BLOCK), 0, h->stream, s, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
     L->have_model = true;
     h->t = 0.0; h->steps_done = 0;
     if (h->log) h->log->step_index = 0;
+    return 0;
+}
+// [A | B] or [C | D] (`cd`) of the handle's copy into fb_linearize's layout, M | N; at(L, n, i, r, c): the kernels' index of (r, c) of system i
+template <class At>
+static int32_t lss_unpad(const char* verb, fb_handle h, bool cd, double* M, double* N, At at) {
+    if (!h) return fail("null handle");
+    if (!is_lss(h)) return fail("%s: the handle is not a LinearizedSS handle (fb_lss_create)", verb);
+    if (int32_t rc = lss_ready(h)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const LssState* L = h->lss;
+    const int64_t n = h->n;
+    const int nx = L->nx, nu = L->nu, rows = cd ? L->ny : nx;
+    std::vector<double> buf((size_t)(cd ? (nx + nu) * L->ny : (L->G + nu) * L->G) * n);
+    HIPCHK(hipMemcpyAsync(buf.data(), cd ? L->cd : L->ab, sizeof(double) * buf.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < nx + nu; c++) {
+        double* out = c < nx ? M : N;
+        if (!out) continue;
+        for (int r = 0; r < rows; r++)
+            for (int64_t i = 0; i < n; i++) out[((int64_t)r + (int64_t)rows * (c < nx ? c : c - nx)) * n + i] = buf[at(L, n, i, r, c)];
+    }
     return 0;
 }
 // sizes are checked before anything touches a device
@@ -155,18 +222,18 @@ static int32_t lss_check_dims(int32_t nx, int32_t nu, int32_t ny, int64_t n) {
 }
 static int32_t lss_new_handle(int32_t nx, int32_t nu, int32_t ny, int64_t n, int32_t device_id, fb_handle* out) {
     HIPCHK(hipSetDevice(device_id));
-    fb_handle h = new fb_handle_s();
+    NewHandle made;
+    fb_handle h = made.h = new fb_handle_s();
     h->model = FB_MODEL_LSS; h->kin = FB_KIN_WA; h->dtype = FB_F64; h->device = device_id; h->n = n;
     h->params.dt = 0.02; h->params.periodic_n = 1; h->params.surface = 0;
     h->params.T_sl = isa::T_std; h->params.p_sl = isa::p_std;
     h->params.wind_ned[0] = h->params.wind_ned[1] = h->params.wind_ned[2] = 0.0;
     h->params.h_terrain = 0.0;
-    auto bail = [&](int32_t rc) { const std::string msg = g_err; fb_destroy(h); g_err = msg; return rc; };
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail("fb_lss_create: hipStreamCreateWithFlags failed"));
+    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return fail("fb_lss_create: hipStreamCreateWithFlags failed");
     h->stream = h->own_stream;
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail("fb_lss_create: hipEventCreate failed"));
-    if (int32_t rc = lss_create(h, nx, nu, ny)) return bail(rc);
-    *out = h;
+    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return fail("fb_lss_create: hipEventCreate failed");
+    if (int32_t rc = lss_create(h, nx, nu, ny)) return rc;
+    *out = made.release();
     return 0;
 }
 
@@ -192,8 +259,9 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
     const LssState* L = h->lss;
     const int64_t n = h->n, nx = L->nx, nu = L->nu, ny = L->ny, nc = nx + nu;
     // staged on the device in the layout fb_linearize writes, then k_lss_gather with every index: one path for both ways in
+    DevBlocks blocks;
     double* st = nullptr;
-    HIPCHK(hipMalloc(&st, sizeof(double) * (size_t)(2 * nx + nu + ny + (nx + ny) * nc) * n));
+    if (int32_t rc = blocks.alloc(&st, (size_t)(2 * nx + nu + ny + (nx + ny) * nc) * n)) return rc;
     fbl::LssSrc s;
     double* p = st;
     int32_t rc = 0;
@@ -209,7 +277,6 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
     s.snx = (int)nx; s.snu = (int)nu; s.sny = (int)ny; s.idx = nullptr;
     if (!rc) rc = lss_gather(h, s, nullptr, nullptr, nullptr);
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(st);
     return rc;
 }
 
@@ -245,17 +312,18 @@ int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, 
     if (!in_range(ix, nx, snx, "state") || !in_range(iu, nu, snu, "input") || !in_range(iy, ny, sny, "output")) return -1;
     HIPCHK(hipSetDevice(src->device));
     HIPCHK(hipStreamSynchronize(src->stream));   // (the result the new handle's stream is about to read)
-    fb_handle h = nullptr;
-    if (int32_t rc = lss_new_handle(nx, nu, ny, src->n, src->device, &h)) return rc;
+    NewHandle made;
+    if (int32_t rc = lss_new_handle(nx, nu, ny, src->n, src->device, &made.h)) return rc;
+    const fb_handle h = made.h;
     const int64_t n = src->n;
     fbl::LssSrc s;
     s.xdot0 = src->lin_buf; s.x0 = s.xdot0 + (int64_t)snx * n; s.u0 = s.x0 + (int64_t)snx * n; s.y0 = s.u0 + (int64_t)snu * n;
     s.AB = s.y0 + (int64_t)sny * n; s.CD = s.AB + (int64_t)snx * (snx + snu) * n;   // (lin_run's rows)
     s.snx = snx; s.snu = snu; s.sny = sny; s.idx = nullptr;
-    if (int32_t rc = lss_gather(h, s, ix, iu, iy)) { const std::string msg = g_err; fb_destroy(h); g_err = msg; return rc; }
+    if (int32_t rc = lss_gather(h, s, ix, iu, iy)) return rc;
     h->params.dt = src->params.dt;
     if (src->stream != src->own_stream) h->stream = src->stream;   // (a source that runs on its caller's stream: so does the model made from it)
-    *out = h;
+    *out = made.release();
     return 0;
 }
 

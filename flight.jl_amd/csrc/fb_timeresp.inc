@@ -1,9 +1,7 @@
 // fb_timeresp.inc — step responses and StepInfo of a Model(lss) batch (include/flightbatch.h: fb_lss_stepinfo; kernels: timeresp_kernels.hpp;
-// docs/design/linearize.md, "Step responses on the device"). Included by fb_capi.hip after fb_poles.inc.
+// docs/design/linearize.md, "Step responses on the device"). Included by fb_capi.hip after fb_lss.inc (the verbs' shared scaffold).
 // Reference: FA design/robot2d/robot2d_design.ipynb calls step(P[:y, :u], t_sim) and stepinfo of it on the velocity loop and on the position
 // loop; here one call does so for m channels of every system of a batch, and flightbatch/timeresp.py prints the reference's table.
-
-static int timeresp_group(int rows) { return rows <= 8 ? 8 : rows <= 16 ? 16 : 32; }
 
 extern "C" {
 
@@ -14,17 +12,12 @@ int32_t fb_lss_stepinfo_samples(int32_t nsteps, int32_t stride) {
 
 int32_t fb_lss_stepinfo(fb_handle h, const int32_t* iu, const int32_t* iy, int32_t m, double t_sim, double dt, const double* opts,
                         const double* y0_in, const double* yf_in, int32_t stride, double* y, double* info, int32_t* status) {
-    if (!h) return fail("null handle");
-    if (!is_lss(h)) return fail("fb_lss_stepinfo: the handle is not a LinearizedSS handle (FB_MODEL_LSS: fb_lss_create, fb_lss_from_linearization)");
+    if (int32_t rc = verb_handle("fb_lss_stepinfo", h, FB_STEPINFO_NX_MAX, "call", "FB_STEPINFO_NX_MAX: one lane of a group of 32 is the output's")) return rc;
     const LssState* L = h->lss;
-    if (!L) return fail("fb_lss_stepinfo: the handle is not ready (its creation did not finish)");
-    const int nx = L->nx;
-    if (nx < 1 || nx > FB_STEPINFO_NX_MAX)
-        return fail("fb_lss_stepinfo: nx = %d, the call takes 1 <= nx <= %d (FB_STEPINFO_NX_MAX: one lane of a group of 32 is the output's)", nx, (int)FB_STEPINFO_NX_MAX);
     if (m < 1 || m > 64) return fail("fb_lss_stepinfo: m = %d, a call takes 1 <= m <= 64 channels", (int)m);
     if (h->n * (int64_t)m > ((int64_t)1 << 31) - 1)
         return fail("fb_lss_stepinfo: %lld systems x %d channels exceed the 2^31 - 1 pairs of one launch grid", (long long)h->n, (int)m);
-    if (!L->have_model) return fail("fb_lss_stepinfo: this LinearizedSS handle has no model yet (fb_lss_set_model)");
+    if (int32_t rc = verb_model("fb_lss_stepinfo", h)) return rc;
     if (!iu || !iy) return fail("fb_lss_stepinfo: iu and iy are required");
     for (int j = 0; j < m; j++) {
         if (iu[j] < 0 || iu[j] >= L->nu) return fail("fb_lss_stepinfo: iu[%d] = %d is outside [0, %d)", j, (int)iu[j], L->nu);
@@ -45,40 +38,27 @@ int32_t fb_lss_stepinfo(fb_handle h, const int32_t* iu, const int32_t* iy, int32
     // one device block: y0_in | yf_in | y | info, then the int32 words status | iu | iy
     const size_t n_y0 = y0_in ? nc : 0, n_yf = yf_in ? nc : 0, n_y = y ? (size_t)ns * nc : 0;
     const size_t nd = n_y0 + n_yf + n_y + 9 * nc, ni = nc + 2 * (size_t)m;
+    DevBlocks blocks;
     double* d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(double) * nd + sizeof(int32_t) * ni));
-    auto run = [&]() -> int32_t {
-        double *d_y0 = d, *d_yf = d_y0 + n_y0, *d_y = d_yf + n_yf, *d_info = d_y + n_y;
-        int32_t *d_st = reinterpret_cast<int32_t*>(d + nd), *d_iu = d_st + nc, *d_iy = d_iu + m;
-        if (y0_in) HIPCHK(hipMemcpyAsync(d_y0, y0_in, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
-        if (yf_in) HIPCHK(hipMemcpyAsync(d_yf, yf_in, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d_iu, iu, sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d_iy, iy, sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream));
-        fbt::TimeRespArgs a = {};
-        a.ab = L->ab; a.cd = L->cd; a.iu = d_iu; a.iy = d_iy;
-        a.y0_in = y0_in ? d_y0 : nullptr; a.yf_in = yf_in ? d_yf : nullptr; a.y = y ? d_y : nullptr; a.info = d_info; a.status = d_st;
-        a.n = h->n; a.nx = nx; a.nu = L->nu; a.ny = L->ny; a.G = L->G; a.m = m; a.nsteps = N; a.stride = stride; a.ns = ns;
-        a.dt = dt; a.settling_th = th; a.rise_lo = lo; a.rise_hi = hi;
-        const int P = timeresp_group(nx + 1);
-        const dim3 grid = grid_for((int64_t)nc, fbt::TR_WAVE / P), block(fbt::TR_WAVE);
-        const bool stamp = h->timing && h->lev_used < h->lev_max;
-        if (stamp) HIPCHK(hipEventRecord(h->lev[2 * h->lev_used], h->stream));
-        if (P == 8) hipLaunchKernelGGL(fbt::k_timeresp<8>, grid, block, 0, h->stream, a);
-        else if (P == 16) hipLaunchKernelGGL(fbt::k_timeresp<16>, grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL(fbt::k_timeresp<32>, grid, block, 0, h->stream, a);
-        if (stamp) { HIPCHK(hipEventRecord(h->lev[2 * h->lev_used + 1], h->stream)); h->lev_used++; }
-        HIPCHK(hipGetLastError());
-        if (y) HIPCHK(hipMemcpyAsync(y, d_y, sizeof(double) * n_y, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(info, d_info, sizeof(double) * 9 * nc, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return 0;
-    };
-    const int32_t rc = run();
-    const std::string msg = g_err;
-    (void)hipFree(d);
-    g_err = msg;
-    return rc;
+    if (int32_t rc = blocks.alloc(&d, nd + (ni + 1) / 2)) return rc;   // (the int32 words behind the doubles)
+    double *d_y0 = d, *d_yf = d_y0 + n_y0, *d_y = d_yf + n_yf, *d_info = d_y + n_y;
+    int32_t *d_st = reinterpret_cast<int32_t*>(d + nd), *d_iu = d_st + nc, *d_iy = d_iu + m;
+    if (y0_in) HIPCHK(hipMemcpyAsync(d_y0, y0_in, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+    if (yf_in) HIPCHK(hipMemcpyAsync(d_yf, yf_in, sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_iu, iu, sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_iy, iy, sizeof(int32_t) * m, hipMemcpyHostToDevice, h->stream));
+    fbt::TimeRespArgs a = {};
+    verb_args(a, h);
+    a.iu = d_iu; a.iy = d_iy;
+    a.y0_in = y0_in ? d_y0 : nullptr; a.yf_in = yf_in ? d_yf : nullptr; a.y = y ? d_y : nullptr; a.info = d_info; a.status = d_st;
+    a.m = m; a.nsteps = N; a.stride = stride; a.ns = ns;
+    a.dt = dt; a.settling_th = th; a.rise_lo = lo; a.rise_hi = hi;
+    if (int32_t rc = family_launch(h, group_for(a.nx + 1), (int64_t)nc, a, [](auto P) { return fbt::k_timeresp<P.value>; })) return rc;
+    if (y) HIPCHK(hipMemcpyAsync(y, d_y, sizeof(double) * n_y, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(info, d_info, sizeof(double) * 9 * nc, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 }  // extern "C"

@@ -6,27 +6,26 @@
 // lane r owns row r of Z. With h = P / 2 the four blocks of H sit at fixed register offsets: rows and columns [0, nx) and [h, h + nx) are the
 // Hamiltonian, the others are padding (diagonal -1, held; never a pivot, so not in the determinant; the live rows' padding columns stay 0).
 //
-// inv(Z): in-place Gauss-Jordan elimination, every step k a compile-time k (the row is a register array). Pivot of step k: the group-wide
-// maximum of |Z_ik| over the rows not yet used (butterfly of cross-lane reads), then the lowest lane that holds it (ballot) — a function of the
-// group's values only. The rows stay with their lanes (implicit pivoting): with sigma(k) the pivot lane of step k the elimination leaves
+// inv(Z): in-place Gauss-Jordan elimination, every step k a compile-time k (the row is a register array). Pivot of step k: the family's rule
+// on |Z_ik| (fbg::Lanes::pivot, lss_group.hpp). The rows stay with their lanes (implicit pivoting): with sigma(k) the pivot lane of step k the elimination leaves
 // S[sigma(i)][j] = inv(Z)[i][sigma(j)], which one pass through the group's LDS panel undoes. The pivot lane publishes its scaled row in that
 // panel and every lane reads it back as P / 2 16-byte broadcasts. The panel belongs to one wave: fences and wave_barrier, no s_barrier.
 // Lanes past the batch's end design the last system again and store nothing, so a wave never diverges on the batch size.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <float.h>
+#include "lss_group.hpp"
 #include "../../include/flightbatch.h"
 
 namespace fbq {
 
-constexpr int LQR_WAVE = 64;
+using namespace fbg;
+
+constexpr int LQR_WAVE = fbg::WAVE;
 constexpr int LQR_NU_MAX = 8;
 constexpr int LQR_MAX_ITERS = 50;
 constexpr double LQR_TOL = 1e-13;
 
 struct LqrArgs {
-    const double* ab;      // the handle's [A | B] (lss_kernels.hpp), with its group size G
+    const double* ab;      // the handle's [A | B] (fbg::ab_index, lss_group.hpp), with its group size G
     const double* q;       // Q, nx x nx column-major (symmetric)
     double *K, *X, *resid; // outputs in fb_linearize's layout, any may be null
     int32_t *iters, *status;
@@ -36,36 +35,20 @@ struct LqrArgs {
     double rinv[LQR_NU_MAX * LQR_NU_MAX];   // inv(R), element (a, b) at [a nu + b] (symmetric)
 };
 
-// the wave's LDS operations are performed in the order they are issued: only the compiler has to be kept from moving them (lss_kernels.hpp)
-__device__ inline void panel_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ inline bool is_fin(double v) { return fabs(v) <= DBL_MAX; }   // false for NaN
-
+// the lane group with the LDS panels of k_lqr and k_lss_freqresp
 template <int P>
-struct Group {
+struct Group : fbg::Lanes<P> {
     static constexpr int h = P / 2, LD = P + 1;   // (an odd row pitch: a lane per row or a lane per column, neither collides on a bank)
     static constexpr int PANEL = P * LD, SIDE = LQR_NU_MAX * h;
     double* pan;    // P x LD
     double* ya;     // nu x h: scratch matrices of the prologue and epilogue, (a, c) at [a h + c]
     double* kb;
     int* sig;       // sigma
-    int r, base;
     __device__ Group(double* lds_d, int* lds_i) {
         const int g = threadIdx.x / P;
-        r = threadIdx.x % P; base = g * P;
         pan = lds_d + g * (PANEL + 2 * SIDE); ya = pan + PANEL; kb = ya + SIDE;
         sig = lds_i + g * P;
     }
-    __device__ double gmax(double v) const {
-#pragma unroll
-        for (int o = P / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, P));
-        return v;
-    }
-    __device__ unsigned mask(bool b) const { return (unsigned)((__ballot(b) >> base) & (P == 32 ? 0xffffffffull : ((1ull << P) - 1))); }
-    __device__ bool any(bool b) const { return mask(b) != 0; }
 };
 
 // w <- inv(w) over the live rows and columns k < KL with k % h < nx (`live`: this lane owns such a row); logdet += sum log|pivot|.
@@ -80,13 +63,10 @@ __device__ inline bool gj_inverse(double (&w)[P], const Group<P>& g, bool live, 
 #pragma unroll
     for (int k = 0; k < KL; k++) {
         if (k % h < nx) {
-            const double v = used ? -1.0 : fabs(w[k]);
-            const double m = g.gmax(v);
-            const unsigned cand = g.mask(!used && v == m);
-            ok = ok && cand != 0 && m > 0.0 && is_fin(m);
-            const int p = cand ? __builtin_ctz(cand) : k;
+            const Pivot pv = g.pivot(used, used ? -1.0 : fabs(w[k]), k);
+            ok = ok && pv.found;
             panel_sync();
-            if (g.r == p) {
+            if (g.r == pv.p) {
                 const double ip = 1.0 / w[k];
 #pragma unroll
                 for (int j = 0; j < P; j++) w[j] = j == k ? ip : w[j] * ip;
@@ -96,7 +76,7 @@ __device__ inline bool gj_inverse(double (&w)[P], const Group<P>& g, bool live, 
                 used = true; myk = k;
             }
             panel_sync();
-            if (g.r != p) {
+            if (g.r != pv.p) {
                 const double f = w[k];
                 const double2* row = reinterpret_cast<const double2*>(g.pan);
 #pragma unroll
@@ -106,7 +86,7 @@ __device__ inline bool gj_inverse(double (&w)[P], const Group<P>& g, bool live, 
                     w[j + 1] = j + 1 == k ? -f * s.y : fma(-f, s.y, w[j + 1]);
                 }
             }
-            logdet += log(m);
+            logdet += log(pv.m);
         }
     }
     // S[sigma(i)][j] -> inv[i][sigma(j)]
@@ -135,7 +115,7 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
 
     // ---- H: G = B inv(R) B' through the side panels (kb: B', ya: inv(R) B')
     if (tact) {
-        for (int b = 0; b < nu; b++) g.kb[b * h + r] = a.ab[(int64_t)(a.G + b) * S + slot0 + r];
+        for (int b = 0; b < nu; b++) g.kb[b * h + r] = a.ab[ab_index(S, slot0, a.G + b) + r];
     }
     panel_sync();
     if (tact) {
@@ -156,7 +136,7 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
 #pragma unroll
         for (int c = 0; c < h; c++) {
             if (c < nx) {
-                z[c] = a.ab[(int64_t)c * S + slot0 + r];
+                z[c] = a.ab[ab_index(S, slot0, c) + r];
                 double acc = 0.0;
                 for (int b = 0; b < nu; b++) acc = fma(g.ya[b * h + r], g.kb[b * h + c], acc);
                 z[h + c] = -acc;
@@ -167,7 +147,7 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
         for (int c = 0; c < h; c++) {
             if (c < nx) {
                 z[c] = -a.q[rr + nx * c];
-                z[h + c] = -a.ab[(int64_t)rr * S + slot0 + c];
+                z[h + c] = -a.ab[ab_index(S, slot0, rr) + c];
             }
         }
     }
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
     panel_sync();
     if (tact) {
         for (int b = 0; b < nu; b++) {
-            const double* bcol = a.ab + (int64_t)(a.G + b) * S + slot0;
+            const double* bcol = a.ab + ab_index(S, slot0, a.G + b);
             double acc = 0.0;
 #pragma unroll
             for (int m = 0; m < h; m++)
@@ -269,7 +249,7 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
     if (tact) {
 #pragma unroll
         for (int c = 0; c < h; c++)
-            if (c < nx) g.pan[r * LD + c] = a.ab[(int64_t)c * S + slot0 + r];
+            if (c < nx) g.pan[r * LD + c] = a.ab[ab_index(S, slot0, c) + r];
     }
     panel_sync();
     double t[h];

@@ -4,21 +4,16 @@
 // lane r of a group owns state row r. Lanes r >= nx and columns c >= nx are padding: their matrix entries, xdot0 and x0 are exact zeros in
 // the handle's copy of the model, so their dx stays 0 and contributes a * 0 = 0.
 //
-// The handle's copy of the model (written by k_lss_gather only), with slot = i G + r and S = n G:
-//   ab [(G + nu) x S]   column c of row r of [A | B] at ab[c S + slot] (A's columns zero-padded to G): a lane's loads are coalesced
-//   xs [2 x S]          xdot0_r, x0_r
-//   u0 [nu x n], y0 [ny x n]
-//   cd [(nx + nu) x n x ny]   element (j, c) of [C | D] at cd[(c n + i) ny + j]: the lanes of a group read consecutive rows j
-// State, inputs, outputs and derivative are the C ABI's rows: x [nx x n], u [nu x n], y [ny x n], xdot [nx x n].
+// The layout of the handle's copy of the model (written by k_lss_gather only) is stated once, at fbg::ab_index and fbg::cd_index
+// (lss_group.hpp), and read and written through them. State, inputs, outputs and derivative are the C ABI's rows: x [nx x n], u [nu x n], y [ny x n], xdot [nx x n].
 //
-// Exchange of the G stage values inside a group (docs/design/linearize.md, "Model(lss) on the device"): XCH = 0, an LDS panel of one double
-// per lane, written once per stage and read back as G / 2 16-byte broadcasts; XCH = 1, G cross-lane reads (__shfl, two ds_bpermute_b32
-// each) and no LDS. Both are instantiated; FLIGHTBATCH_LSS_EXCHANGE selects at create time (default: the panel).
+// Exchange of the G stage values: fbg::Exchange<G, XCH> (lss_group.hpp), both instantiated; FLIGHTBATCH_LSS_EXCHANGE selects at create time.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "lss_group.hpp"
 
 namespace fbl {
+
+using fbg::Exchange;
 
 constexpr int LSS_BLOCK = 256;
 constexpr int LSS_NX_MAX = 32, LSS_NU_MAX = 8, LSS_NY_MAX = 64;
@@ -31,44 +26,12 @@ struct LssArgs {
     double dt;
 };
 
-// the G values dz of this lane's group, one per lane, as seen by every lane of the group: out[c] = dz of lane c
-template <int G, int XCH>
-struct Exchange {
-    double* row;       // XCH == 0: this group's G doubles of the panel
-    double* mine;
-    __device__ Exchange(double* panel) : row(panel + (threadIdx.x / G) * G), mine(panel + threadIdx.x) {}
-    // acc + sum_c a[c] dz_c, c ascending
-    __device__ double dot(const double (&a)[G], double dz, double acc) const {
-        if constexpr (XCH == 0) {
-            // the panel belongs to one wave (a group never straddles one): the wave's LDS operations are performed in the order they are
-            // issued, so only the compiler has to be kept from moving them across each other
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            *mine = dz;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const double2* p = reinterpret_cast<const double2*>(row);
-#pragma unroll
-            for (int c = 0; c < G; c += 2) {
-                const double2 v = p[c / 2];
-                acc = fma(a[c], v.x, acc);
-                acc = fma(a[c + 1], v.y, acc);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < G; c++) acc = fma(a[c], __shfl(dz, c, G), acc);
-        }
-        return acc;
-    }
-};
-
 // the constant of a launch: xdot0_r + sum_c B_rc (u_c - u0_c), c ascending (u is held over the launch)
 template <int G>
 __device__ inline double lss_const(const LssArgs& a, int64_t i, int64_t slot) {
     const int64_t S = a.n * G;
     double c0 = a.xs[slot];
-    for (int c = 0; c < a.nu; c++) c0 = fma(a.ab[(int64_t)(G + c) * S + slot], a.u[(int64_t)c * a.n + i] - a.u0[(int64_t)c * a.n + i], c0);
+    for (int c = 0; c < a.nu; c++) c0 = fma(a.ab[fbg::ab_index(S, slot, G + c)], a.u[(int64_t)c * a.n + i] - a.u0[(int64_t)c * a.n + i], c0);
     return c0;
 }
 
@@ -82,7 +45,7 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_rk4(LssArgs a, int nsteps) {
     const int64_t S = a.n * G, slot = i * G + r;
     double arow[G];
 #pragma unroll
-    for (int c = 0; c < G; c++) arow[c] = a.ab[(int64_t)c * S + slot];
+    for (int c = 0; c < G; c++) arow[c] = a.ab[fbg::ab_index(S, slot, c)];
     const double x0 = a.xs[S + slot], c0 = lss_const<G>(a, i, slot);
     const bool live = r < a.nx;
     double x = live ? a.x[(int64_t)r * a.n + i] : 0.0;
@@ -111,16 +74,16 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_f_ode(LssArgs a) {
     const double x = live ? a.x[(int64_t)r * a.n + i] : 0.0;
     double arow[G];
 #pragma unroll
-    for (int c = 0; c < G; c++) arow[c] = a.ab[(int64_t)c * S + slot];
+    for (int c = 0; c < G; c++) arow[c] = a.ab[fbg::ab_index(S, slot, c)];
     const Exchange<G, 0> ex(panel);
     const double xd = ex.dot(arow, x - a.xs[S + slot], lss_const<G>(a, i, slot));   // (the stepper's own expression: same bits as its k1)
     if (live && a.xdot) a.xdot[(int64_t)r * a.n + i] = xd;
     const double* dx = ex.row;   // the group's dx, left in the panel by dot()
     for (int j = r; j < a.ny; j += G) {
         double acc = a.y0[(int64_t)j * a.n + i];
-        for (int c = 0; c < a.nx; c++) acc = fma(a.cd[((int64_t)c * a.n + i) * a.ny + j], dx[c], acc);
+        for (int c = 0; c < a.nx; c++) acc = fma(a.cd[fbg::cd_index(a.n, i, a.ny, j, c)], dx[c], acc);
         for (int c = 0; c < a.nu; c++)
-            acc = fma(a.cd[((int64_t)(a.nx + c) * a.n + i) * a.ny + j], a.u[(int64_t)c * a.n + i] - a.u0[(int64_t)c * a.n + i], acc);
+            acc = fma(a.cd[fbg::cd_index(a.n, i, a.ny, j, a.nx + c)], a.u[(int64_t)c * a.n + i] - a.u0[(int64_t)c * a.n + i], acc);
         a.y[(int64_t)j * a.n + i] = acc;
     }
 }
@@ -155,9 +118,9 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_gather(LssSrc s, LssDst d) {
         d.xs[S + slot] = x0;
         if (live) d.x[(int64_t)r * n + i] = x0;
         for (int c = 0; c < G; c++)
-            d.ab[(int64_t)c * S + slot] = (live && c < d.nx) ? s.AB[((int64_t)sr + (int64_t)s.snx * ix[c]) * n + i] : 0.0;
+            d.ab[fbg::ab_index(S, slot, c)] = (live && c < d.nx) ? s.AB[((int64_t)sr + (int64_t)s.snx * ix[c]) * n + i] : 0.0;
         for (int c = 0; c < d.nu; c++)
-            d.ab[(int64_t)(G + c) * S + slot] = live ? s.AB[((int64_t)sr + (int64_t)s.snx * (s.snx + iu[c])) * n + i] : 0.0;
+            d.ab[fbg::ab_index(S, slot, G + c)] = live ? s.AB[((int64_t)sr + (int64_t)s.snx * (s.snx + iu[c])) * n + i] : 0.0;
     }
     for (int c = 0; c < d.nu; c++) {
         const double u0 = s.u0[(int64_t)iu[c] * n + i];
@@ -169,7 +132,7 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_gather(LssSrc s, LssDst d) {
         d.y0[(int64_t)j * n + i] = s.y0[(int64_t)sj * n + i];
         for (int c = 0; c < d.nx + d.nu; c++) {
             const int sc = c < d.nx ? ix[c] : s.snx + iu[c - d.nx];
-            d.cd[((int64_t)c * n + i) * d.ny + j] = s.CD[((int64_t)sj + (int64_t)s.sny * sc) * n + i];
+            d.cd[fbg::cd_index(n, i, d.ny, j, c)] = s.CD[((int64_t)sj + (int64_t)s.sny * sc) * n + i];
         }
     }
 }

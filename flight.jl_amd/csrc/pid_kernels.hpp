@@ -13,29 +13,27 @@
 // unstable loop shows as FB_PID_DIVERGED; NLopt's optimisers are not restated (the search is host-side, flightbatch/pidopt.py).
 //
 // k_lss_freqresp: one (system, frequency) pair per group of P lanes of one wave (P = 8, 16 or 32, the smallest >= nx); lane r owns the complex
-// row r of [jw I - A | b]. Gauss-Jordan with the pivot rule of gj_inverse (lqr_kernels.hpp): the group-wide maximum of |z|^2 over the rows
-// not yet used, the lowest lane that holds it; the scaled pivot row goes through the group's LDS panel and is read back as 16-byte
+// row r of [jw I - A | b]. Gauss-Jordan with the family's pivot rule (fbg::Lanes::pivot, lss_group.hpp) on |z|^2; the scaled pivot row goes through the group's LDS panel and is read back as 16-byte
 // broadcasts. Every step has a compile-time index: the rows are register arrays.
 // k_pid_metrics: one (system, candidate) pair per group of P lanes (P >= nx + 4). Lanes 0 .. nx + 1 own the rows of the closed loop (the plant
 // rows with the rank-one feedback folded in, then xi, then eta), lanes nx + 2 and nx + 3 the output rows of y and u: the broadcast dot
 // product that is the first stage of a step is, on those two lanes, the sample y_k, u_k. Stage values travel as in k_lss_rk4 (Exchange<G, 0>).
 // Lanes past the batch's end work on the last pair again and store nothing, so a wave never diverges on the batch size.
 #pragma once
-#include "lss_kernels.hpp"
-#include "lqr_kernels.hpp"
+#include "lss_group.hpp"
+#include "lqr_kernels.hpp"   // fbq::Group: k_lss_freqresp uses its panels
 
 namespace fbp {
 
 using fbq::Group;
-using fbq::is_fin;
-using fbq::panel_sync;
+using namespace fbg;
 
-constexpr int PID_WAVE = 64;
+constexpr int PID_WAVE = fbg::WAVE;
 constexpr double PID_MS_MAX = 1e3;      // pidopt.jl:43
 constexpr double PID_BLOWUP = 1e12;     // |y| or |u| beyond this: FB_PID_DIVERGED
 
 struct FreqArgs {
-    const double* ab; const double* cd;   // the handle's copies (lss_kernels.hpp), G its group size
+    const double* ab; const double* cd;   // the handle's copies (fbg::ab_index, lss_group.hpp), G its group size
     const double* w;                      // [nw]
     double *re, *im;                      // [nw x n], system index fastest; NaN where a pivot was zero or not finite
     int64_t n;
@@ -75,10 +73,10 @@ __global__ __launch_bounds__(PID_WAVE) void k_lss_freqresp(FreqArgs a) {
     double zr[P], zi[P];
 #pragma unroll
     for (int c = 0; c < P; c++) {
-        zr[c] = (live && c < nx) ? -a.ab[(int64_t)c * S + slot0 + r] : 0.0;
+        zr[c] = (live && c < nx) ? -a.ab[ab_index(S, slot0, c) + r] : 0.0;
         zi[c] = c == r ? om : 0.0;
     }
-    double br = live ? a.ab[(int64_t)(a.G + a.iu) * S + slot0 + r] : 0.0, bi = 0.0;
+    double br = live ? a.ab[ab_index(S, slot0, a.G + a.iu) + r] : 0.0, bi = 0.0;
 
     bool used = !live, ok = true;
     int myk = r;
@@ -86,14 +84,11 @@ __global__ __launch_bounds__(PID_WAVE) void k_lss_freqresp(FreqArgs a) {
 #pragma unroll
     for (int k = 0; k < P; k++) {
         if (k < nx) {
-            const double v = used ? -1.0 : fma(zr[k], zr[k], zi[k] * zi[k]);
-            const double m = g.gmax(v);
-            const unsigned cand = g.mask(!used && v == m);
-            ok = ok && cand != 0 && m > 0.0 && is_fin(m);
-            const int p = cand ? __builtin_ctz(cand) : k;
+            const Pivot pv = g.pivot(used, used ? -1.0 : fma(zr[k], zr[k], zi[k] * zi[k]), k);
+            ok = ok && pv.found;
             panel_sync();
-            if (r == p) {
-                const double ipr = zr[k] / m, ipi = -zi[k] / m;   // 1 / z = conj(z) / |z|^2
+            if (r == pv.p) {
+                const double ipr = zr[k] / pv.m, ipi = -zi[k] / pv.m;   // 1 / z = conj(z) / |z|^2
 #pragma unroll
                 for (int j = k + 1; j < P; j++) {
                     const double sr = zr[j] * ipr - zi[j] * ipi, si = zr[j] * ipi + zi[j] * ipr;
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(PID_WAVE) void k_lss_freqresp(FreqArgs a) {
                 used = true; myk = k;
             }
             panel_sync();
-            if (r != p) {
+            if (r != pv.p) {
                 const double fr = zr[k], fi = zi[k];
 #pragma unroll
                 for (int j = k + 1; j < P; j++) {
@@ -125,9 +120,9 @@ __global__ __launch_bounds__(PID_WAVE) void k_lss_freqresp(FreqArgs a) {
     panel_sync();
     if (live) xs[myk] = make_double2(br, bi);
     panel_sync();
-    double pr = a.cd[((int64_t)(nx + a.iu) * a.n + i) * a.ny + a.iy], pi = 0.0;
+    double pr = a.cd[cd_index(a.n, i, a.ny, a.iy, nx + a.iu)], pi = 0.0;
     for (int k = 0; k < nx; k++) {
-        const double ck = a.cd[((int64_t)k * a.n + i) * a.ny + a.iy];
+        const double ck = a.cd[cd_index(a.n, i, a.ny, a.iy, k)];
         const double2 x = xs[k];
         pr = fma(ck, x.x, pr);
         pi = fma(ck, x.y, pi);
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(PID_WAVE) void k_lss_freqresp(FreqArgs a) {
 template <int P>
 __global__ __launch_bounds__(PID_WAVE) void k_pid_metrics(PidArgs a) {
     __shared__ __attribute__((aligned(16))) double panel[PID_WAVE];
-    const Group<P> g(panel, nullptr);   // (for the group's lane index, maximum and ballot only: its panels are never touched here)
+    const fbg::Lanes<P> g;
     constexpr int NG = PID_WAVE / P;
     const int r = g.r, nx = a.nx;
     const int64_t total = a.n * a.m;
@@ -152,22 +147,22 @@ __global__ __launch_bounds__(PID_WAVE) void k_pid_metrics(PidArgs a) {
     const int64_t i = q % a.n;
     const int64_t S = a.n * a.G, slot0 = i * a.G;
     const double kp = a.pid[q], ki = a.pid[total + q], kd = a.pid[2 * total + q], tf = a.pid[3 * total + q];
-    const double d = a.cd[((int64_t)(nx + a.iu) * a.n + i) * a.ny + a.iy];
+    const double d = a.cd[cd_index(a.n, i, a.ny, a.iy, nx + a.iu)];
     const double kdt = kd / tf, Dc = kp + kdt, den = 1.0 + d * Dc, gg = 1.0 / den;
     const bool singular_loop = !(den != 0.0) || !is_fin(gg);
     const double uc = gg * Dc, yc = d * uc;   // u = uc + urow . z, y = yc + yrow . z with z = (x, xi, eta)
 
     // this lane's row of the closed loop, or of the outputs
     const bool plant = r < nx, state = r < nx + 2;
-    const double br = plant ? a.ab[(int64_t)(a.G + a.iu) * S + slot0 + r] : 0.0;
+    const double br = plant ? a.ab[ab_index(S, slot0, a.G + a.iu) + r] : 0.0;
     double row[P];
 #pragma unroll
     for (int c = 0; c < P; c++) {
-        const double cc = c < nx ? a.cd[((int64_t)c * a.n + i) * a.ny + a.iy] : 0.0;
+        const double cc = c < nx ? a.cd[cd_index(a.n, i, a.ny, a.iy, c)] : 0.0;
         const double ur = gg * (c < nx ? -Dc * cc : c == nx ? ki : c == nx + 1 ? -kdt : 0.0);
         const double yr = cc + d * ur;
         double v = 0.0;
-        if (plant) v = (c < nx ? a.ab[(int64_t)c * S + slot0 + r] : 0.0) + br * ur;
+        if (plant) v = (c < nx ? a.ab[ab_index(S, slot0, c) + r] : 0.0) + br * ur;
         else if (r == nx) v = -yr;
         else if (r == nx + 1) v = (-yr - (c == nx + 1 ? 1.0 : 0.0)) / tf;
         else if (r == nx + 2) v = yr;
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(PID_WAVE) void k_pid_metrics(PidArgs a) {
 
     // ---- the step response: N steps of RK4; the first stage of step k is, on the output lanes, sample k
     const double dt = a.dt, hdt = a.dt / 2, dt6 = a.dt / 6;
-    const fbl::Exchange<P, 0> ex(panel);
+    const fbg::Exchange<P, 0> ex(panel);
     double x = 0.0, sum = 0.0, peak = 0.0, last = 0.0;
     bool blown = false;
 #pragma unroll 1
@@ -188,10 +183,7 @@ __global__ __launch_bounds__(PID_WAVE) void k_pid_metrics(PidArgs a) {
         sum += k == 0 ? 0.5 * f : f;
         peak = fmax(peak, f);
         blown = blown || !(fabs(k1) <= PID_BLOWUP);
-        const double k2 = ex.dot(row, state ? x + hdt * k1 : 0.0, c0);
-        const double k3 = ex.dot(row, state ? x + hdt * k2 : 0.0, c0);
-        const double k4 = ex.dot(row, state ? x + dt * k3 : 0.0, c0);
-        x = state ? x + dt6 * (2 * (k2 + k3) + (k1 + k4)) : 0.0;
+        x = fbg::rk4_finish<P>(ex, row, c0, state, x, k1, dt, hdt, dt6);
     }
     {
         const double v = ex.dot(row, x, c0);

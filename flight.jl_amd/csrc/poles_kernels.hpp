@@ -12,15 +12,18 @@
 // or by nx: a group that is finished, or whose input was not finite (its panel is zeroed: it deflates nx zero roots without a sweep), keeps
 // its results until the wave's last group is done. Lanes past the batch's end redo the last system and store nothing.
 #pragma once
-#include "lqr_kernels.hpp"
+#include "lss_group.hpp"
+#include "../../include/flightbatch.h"
 
 namespace fbe {
 
-constexpr int POLES_WAVE = 64;
+using namespace fbg;
+
+constexpr int POLES_WAVE = fbg::WAVE;
 constexpr int POLES_BAL_SWEEPS = 16, POLES_WINDOW_SWEEPS = 30, POLES_BAL_KMAX = 500;
 
 struct PolesArgs {
-    const double* ab;      // the handle's [A | B] (lss_kernels.hpp), with its group size G
+    const double* ab;      // the handle's [A | B] (fbg::ab_index, lss_group.hpp), with its group size G
     double *re, *im;       // [nx x n], sorted; either may be null
     int32_t *iters, *status;
     int64_t n;
@@ -28,34 +31,11 @@ struct PolesArgs {
 };
 
 template <int P>
-__device__ inline double gsum(double v) {
-#pragma unroll
-    for (int o = P / 2; o > 0; o >>= 1) v = v + __shfl_xor(v, o, P);
-    return v;
-}
-// the minimum / maximum over the whole wave of a value that is uniform within each group of P lanes, as a scalar
-template <int P>
-__device__ inline int wave_min(int v) {
-#pragma unroll
-    for (int o = P; o < POLES_WAVE; o <<= 1) v = min(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-template <int P>
-__device__ inline int wave_max(int v) {
-#pragma unroll
-    for (int o = P; o < POLES_WAVE; o <<= 1) v = max(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
-template <int P>
 __global__ __launch_bounds__(POLES_WAVE) void k_poles(PolesArgs a) {
-    using Grp = fbq::Group<P>;
-    using fbq::panel_sync;
-    using fbq::is_fin;
-    constexpr int LD = P + 1, NG = POLES_WAVE / P;
-    __shared__ double lds[NG * Grp::PANEL];
-    Grp g(lds, nullptr);
-    double* const pan = lds + (threadIdx.x / P) * Grp::PANEL;   // (this kernel has no side panels: its own pitch between groups)
+    constexpr int LD = P + 1, PANEL = P * LD, NG = POLES_WAVE / P;
+    __shared__ double lds[NG * PANEL];
+    const fbg::Lanes<P> g;
+    double* const pan = lds + (threadIdx.x / P) * PANEL;
     const int r = g.r, nx = a.nx;
     const int64_t i_own = (int64_t)blockIdx.x * NG + threadIdx.x / P;
     const bool valid = i_own < a.n;
@@ -67,7 +47,7 @@ __global__ __launch_bounds__(POLES_WAVE) void k_poles(PolesArgs a) {
     // ---- the matrix into the panel (rows and columns past nx: zeros); a non-finite entry zeroes the group's panel
     bool fin = true;
     for (int c = 0; c < P; c++) {
-        const double v = (act && c < nx) ? a.ab[(int64_t)c * S + slot0 + r] : 0.0;
+        const double v = (act && c < nx) ? a.ab[ab_index(S, slot0, c) + r] : 0.0;
         fin = fin && is_fin(v);
         at(r, c) = v;
     }

@@ -20,19 +20,18 @@
 // two first crossings and the last sample outside the settling band. Lanes past the batch's end work on the last pair again and store
 // nothing, so a wave never diverges on the batch size.
 #pragma once
-#include "lss_kernels.hpp"
-#include "lqr_kernels.hpp"
+#include "lss_group.hpp"
+#include "../../include/flightbatch.h"
 
 namespace fbt {
 
-using fbq::Group;
-using fbq::is_fin;
+using namespace fbg;
 
-constexpr int TR_WAVE = 64;
+constexpr int TR_WAVE = fbg::WAVE;
 constexpr double TR_BLOWUP = 1e12;      // |y| beyond this: FB_STEPINFO_DIVERGED
 
 struct TimeRespArgs {
-    const double* ab; const double* cd;   // the handle's copies (lss_kernels.hpp), G its group size
+    const double* ab; const double* cd;   // the handle's copies (fbg::ab_index, lss_group.hpp), G its group size
     const int32_t* iu; const int32_t* iy; // [m]
     const double* y0_in; const double* yf_in;   // null or [m x n]; NaN = the first / last sample
     double* y;                            // null or [ns x m x n]: sample s stride at row s, sample N at row ns - 1
@@ -43,20 +42,10 @@ struct TimeRespArgs {
     double dt, settling_th, rise_lo, rise_hi;
 };
 
-// stages 2 .. 4 of a step whose first stage is k1; the output lane and the padding lanes publish 0
-template <int P>
-__device__ inline double rk4_finish(const fbl::Exchange<P, 0>& ex, const double (&row)[P], double c0, bool state, double x, double k1,
-                                    double dt, double hdt, double dt6) {
-    const double k2 = ex.dot(row, state ? fma(hdt, k1, x) : 0.0, c0);
-    const double k3 = ex.dot(row, state ? fma(hdt, k2, x) : 0.0, c0);
-    const double k4 = ex.dot(row, state ? fma(dt, k3, x) : 0.0, c0);
-    return state ? fma(dt6, 2 * (k2 + k3) + (k1 + k4), x) : 0.0;
-}
-
 template <int P>
 __global__ __launch_bounds__(TR_WAVE) void k_timeresp(TimeRespArgs a) {
     __shared__ __attribute__((aligned(16))) double panel[TR_WAVE];
-    const Group<P> g(panel, nullptr);   // (for the group's lane index and ballot only: its panels are never touched here)
+    const fbg::Lanes<P> g;
     constexpr int NG = TR_WAVE / P;
     const int r = g.r, nx = a.nx, N = a.nsteps;
     const int64_t total = a.n * a.m;
@@ -74,15 +63,15 @@ __global__ __launch_bounds__(TR_WAVE) void k_timeresp(TimeRespArgs a) {
     for (int c = 0; c < P; c++) {
         double v = 0.0;
         if (c < nx) {
-            if (state) v = a.ab[(int64_t)c * S + slot0 + r];
-            else if (outlane) v = a.cd[((int64_t)c * a.n + i) * a.ny + iy];
+            if (state) v = a.ab[ab_index(S, slot0, c) + r];
+            else if (outlane) v = a.cd[cd_index(a.n, i, a.ny, iy, c)];
         }
         row[c] = v;
     }
-    const double c0 = state ? a.ab[(int64_t)(a.G + iu) * S + slot0 + r] : outlane ? a.cd[((int64_t)(nx + iu) * a.n + i) * a.ny + iy] : 0.0;
+    const double c0 = state ? a.ab[ab_index(S, slot0, a.G + iu) + r] : outlane ? a.cd[cd_index(a.n, i, a.ny, iy, nx + iu)] : 0.0;
 
     const double dt = a.dt, hdt = a.dt / 2, dt6 = a.dt / 6;
-    const fbl::Exchange<P, 0> ex(panel);
+    const fbg::Exchange<P, 0> ex(panel);
 
     // ---- pass 1: endpoints, extrema at their first index, blow-up; the samples asked for
     double first = 0.0, last = 0.0, mx = -__builtin_inf(), mn = __builtin_inf();

@@ -42,7 +42,7 @@ def test_the_symbols_are_declared_exported_and_bound(fb):
 
 
 def test_the_kernels_are_in_the_library(tmp_path_factory):
-    """exactly the instances the dispatcher of fb_lss_connect can launch (csrc/fb_connect.inc: connect_group), with the resources the doc tabulates"""
+    """exactly the instances the dispatcher of fb_lss_connect can launch (csrc/fb_lss.inc: family_launch, group_for), with the resources the doc tabulates"""
     from support import library_kernels
     ks = library_kernels(tmp_path_factory)
     lds = {"fbc::k_connect<8>": 10240, "fbc::k_connect<16>": 14080, "fbc::k_connect<32>": 11392}
