@@ -21,6 +21,9 @@ from .poles import PolesResult, poles, dampreport  # noqa: F401
 from . import timeresp  # noqa: F401
 from .timeresp import StepInfo, StepResult, stepinfo  # noqa: F401  (the response itself is timeresp.step: `step` is the Simulation verb)
 from .connect import ConnectResult, connect, integrator_world, pid_world, state_feedback, unity_feedback  # noqa: F401
+from . import surgery  # noqa: F401
+from .surgery import (TransformResult, SteadyResult, transform, subsystem_world, delete_vars_world, steady_state, integrators_world,  # noqa: F401
+                      integral_augmentation, lqr_tracker, c172x_design_model)
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)

@@ -5,9 +5,10 @@ docs/design/linearize.md, "LQR design on the device").
     lqr(P, Q, R)                FA design/c172/c172x_design.jl:181, 369, ...   lqr(world, Q, R)            world = LinearWorld(lss) / linear_world(...)
     the loop closed on u = -K x                                              closed_loop(lss, K)         -> LinearizedSS, steps as a LinearWorld
 
-The design scripts' model surgery (the similarity transform to (EAS, α, β, n_eng), the integral augmentation, K_fwd) is host-side numpy on the
+The design scripts' model surgery (the similarity transform to (EAS, α, β, n_eng), the integral augmentation, K_fwd) is on the device in
+flightbatch.surgery (transform, integral_augmentation, steady_state, lqr_tracker); it can still be done in host-side numpy on the
 LinearizedSS before it goes to the device. A model that exists only to be designed on still needs outputs (fb_lss_create wants ny >= 1):
-give it C = I, D = 0, as design_world does."""
+give it C = I, D = 0, as design_model does."""
 from __future__ import annotations
 
 from dataclasses import dataclass, replace

@@ -366,6 +366,37 @@ function connect(p::LinearWorld, c::Union{LinearWorld, Nothing} = nothing; feedb
                 outputs === nothing ? C_NULL : iz, length(iz), status, h))
     return (; world = LinearWorld(h[]), status)
 end
+"`get_design_model!` / `subsystem` / `delete_vars` (FA design/c172/c172x_design.jl:23-82) on the device: the change of state variables x' = y[rows]
+(T = C[rows, :]: T A inv(T), T B, C inv(T), D; x0' = y0[rows], xdot0' = T xdot0 with the 1-based entries `xdot_zero` exactly 0), then the
+subsystem `ix`, `iu`, `iy` (1-based, `nothing`: every index) of the result. `rows = nothing`: T = I, the entries are copied bit for bit. Returns
+the new `LinearWorld`, status (0, FB_SURGERY_SINGULAR = 1 or FB_SURGERY_NOT_FINITE = 2: that system's matrices are NaN) and rpiv (the
+smallest pivot magnitude of T over the largest)."
+function transform(w::LinearWorld, rows = nothing; xdot_zero = Int[], ix = nothing, iu = nothing, iy = nothing)
+    zero_based(v) = v === nothing ? Int32[] : Int32.(v .- 1)
+    jr, jx, ju, jy = zero_based(rows), zero_based(ix), zero_based(iu), zero_based(iy)
+    arg(v, j) = v === nothing ? C_NULL : j
+    mask = zeros(Int32, w.nx); mask[xdot_zero] .= 1
+    status = Vector{Int32}(undef, w.n); rpiv = Vector{Float64}(undef, w.n)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_transform, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int32,
+                                                 Ptr{Int32}, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}),
+                w.handle, arg(rows, jr), mask, arg(ix, jx), length(jx), arg(iu, ju), length(ju), arg(iy, jy), length(jy), status, rpiv, h))
+    return (; world = LinearWorld(h[]), status, rpiv)
+end
+"M = inv([A B; C[z, :] D[z, :]]) and K_fwd = M22 + K M12 (FA design/c172/c172x_design.jl:184-188) on the device: `z` are nu 1-based output
+rows, `k` is nu x nx for the batch, N x nu x nx per system (`lqr`'s) or `nothing`. Returns x = M12 (N x nx x nu), u = M22 (N x nu x nu), k_fwd
+(`nothing` without k), status (as `transform`'s, for L) and rpiv."
+function steady_state(w::LinearWorld, z; k::Union{Array{Float64}, Nothing} = nothing)
+    iz = Int32.(z .- 1)
+    nz = length(iz)
+    x = Array{Float64}(undef, w.n, w.nx, nz); u = Array{Float64}(undef, w.n, w.nu, nz)
+    k_fwd = k === nothing ? nothing : Array{Float64}(undef, w.n, w.nu, nz)
+    status = Vector{Int32}(undef, w.n); rpiv = Vector{Float64}(undef, w.n)
+    check(ccall((:fb_lss_steady, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                              Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iz, nz, k === nothing ? C_NULL : k, k !== nothing && ndims(k) == 3 ? 1 : 0, x, u, k === nothing ? C_NULL : k_fwd, rpiv, status))
+    return (; x, u, k_fwd, status, rpiv)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

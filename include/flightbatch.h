@@ -454,6 +454,36 @@ int32_t fb_lss_connect(fb_handle p, fb_handle c /* NULL: no compensator */, cons
 /* The companion of fb_lss_get_model: C [ny x nx x N] and D [ny x nu x N] of the handle's own copy, in fb_linearize's layout (either may be NULL). */
 int32_t fb_lss_get_cd(fb_handle h, double* C, double* D);
 
+/* ---- design-model surgery on Model(lss) batches (FA design/c172/c172x_design.jl:23-82: get_design_model!, subsystem, delete_vars; :184-188,
+ * :371-381: K_fwd; docs/design/linearize.md, "Design-model surgery on the device") ---------------------------------------------------------
+ * fb_lss_transform: a change of state variables, then a subsystem, of every model of an FB_MODEL_LSS handle into a new FB_MODEL_LSS handle.
+ * rows [nx] names output rows of the source; with T = C[rows, :]
+ *     A' = T A inv(T),  B' = T B,  C' = C inv(T),  D' = D,  x0' = y0[rows],  xdot0' = T xdot0,  u0 and y0 as they are
+ * and the entries r of xdot0' with xdot_zero[r] != 0 are exactly 0 (xdot_zero [nx] may be NULL: none). D[rows, :] is ignored, as the
+ * reference ignores it: the new states are the outputs y[rows] only where those rows of D are zero. Then the lists ix [nxo], iu [nuo],
+ * iy [nyo] select states, inputs and outputs of the transformed model, in the order given (NULL: all of them, the count is ignored). With
+ * rows == NULL, T is the identity and no arithmetic is done: the new handle's entries are copies, bit for bit (subsystem device to device).
+ * status [N] and rpiv [N] may be NULL. status: 0; FB_SURGERY_NOT_FINITE: a non-finite entry of the source's A, B, C, D or xdot0; otherwise
+ * FB_SURGERY_SINGULAR: a zero or non-finite pivot of T (Gauss-Jordan elimination, the pivot of a step the largest magnitude among the rows
+ * not yet used). Such a system gets A', B', C', D' and xdot0' all NaN; the call still returns 0 and no other system changes in any bit.
+ * rpiv: the smallest pivot magnitude over the largest (1 with rows == NULL; 0 for a singular system, NaN for a non-finite one), the
+ * warning of a nearly singular T. The new handle: on the source's device, with its dt and its stream rule (fb_lss_from_linearization), at
+ * x = x0', u = u0, t = 0. The source is only read. Refused, with nothing launched and no handle created: a NULL or non-LSS handle, a handle
+ * without a model, an index of rows outside [0, ny), of ix outside [0, nx), of iu outside [0, nu), of iy outside [0, ny), nxo, nuo or nyo
+ * below 1 or above the source's size, a NULL out.
+ * fb_lss_steady: the steady-state map of every model. iz [nz] names output rows, nz == nu; with L = [A B; C[iz, :] D[iz, :]]
+ *     L [X; U] = [0; I],  K_fwd = U + K X          X [nx x nz] = M12 and U [nu x nz] = M22 of M = inv(L)
+ * K [nu x nx] is a host array, column-major: one matrix for the batch (k_per_system = 0) or one per system in fb_linearize's layout (fb_lqr's
+ * K); NULL: no K_fwd (K_fwd must be NULL as well). X, U, K_fwd come home in fb_linearize's layout, element (i, r, c) at [(r + rows c) N + i];
+ * each of them, rpiv [N] and status [N] may be NULL. status and rpiv as above, for L (NOT_FINITE: an entry of L or of K); X, U, K_fwd of such
+ * a system are NaN. Refused: a NULL or non-LSS handle, a handle without a model, nx + nu > FB_SURGERY_N_MAX, nz != nu, a NULL iz, an index
+ * of iz outside [0, ny), K_fwd without K. */
+enum { FB_SURGERY_SINGULAR = 1, FB_SURGERY_NOT_FINITE = 2, FB_SURGERY_N_MAX = 32 };
+int32_t fb_lss_transform(fb_handle lss, const int32_t* rows, const int32_t* xdot_zero, const int32_t* ix, int32_t nxo, const int32_t* iu, int32_t nuo,
+                         const int32_t* iy, int32_t nyo, int32_t* status, double* rpiv, fb_handle* out);
+int32_t fb_lss_steady(fb_handle lss, const int32_t* iz, int32_t nz, const double* K, int32_t k_per_system, double* X, double* U, double* K_fwd,
+                      double* rpiv, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
