@@ -5,9 +5,9 @@
 //   x = [x_p; x_c]; the stacked model x' = A x + B v, z = C x + D v is block-diagonal. Interconnection v = F z[jz] + G w, outputs z[iz]:
 //   E = inv(I - F D[jz, :]), M = E F C[jz, :], Nw = E G;  A' = A + B M, B' = B Nw, C' = C[iz, :] + D[iz, :] M, D' = D[iz, :] Nw.
 // One system per group of P lanes of one wave (P = 8, 16 or 32, the smallest >= max(nx_p + nx_c, nv); 64 / P systems per wave, one wave per
-// workgroup). Lane r < nv owns row r of [I - F D_jz | F C_jz | G] as three register arrays; Gauss-Jordan elimination on the augmented rows with
-// the family's pivot rule (fbg::Lanes::pivot, lss_group.hpp), every step a
-// compile-time k, the steps k >= nv behind a wave-uniform branch. The rows stay with their lanes: the lane that was the pivot of step k ends
+// workgroup). Lane r < nv owns row r of [I - F D_jz | F C_jz | G] as three register arrays; Gauss-Jordan elimination on the augmented rows,
+// the family's solve (fbg::gj_solve, lss_group.hpp) written out here: through the helper k_connect<8> is 2 % slower than it was
+// (profiles/lss_solve_refactor.txt). The rows stay with their lanes: the lane that was the pivot of step k ends
 // with row k of [M | Nw] and puts it at row k of the group's LDS panel. Lane r < nx then forms row r of [A' | B'], and every lane the output
 // rows r, r + P, ... of [C' | D'], reading [M | Nw] back as broadcasts. The blocks of the stacked model that are zero by construction are
 // skipped, not multiplied; every sum runs with k ascending as explicit fma, so a result is a function of the system's own values only.
@@ -39,20 +39,6 @@ struct ConnectArgs {
     int nf, nw, ny;
 };
 
-// whether every entry of a handle's [A | B] and [C | D] of system i is finite: lane r looks at row r of [A | B] and at rows r, r + P, ... of [C | D]
-template <int P>
-__device__ inline bool side_finite(const ConnectSide& s, int64_t n, int64_t i, int r) {
-    bool fin = true;
-    const int64_t S = n * s.G, slot0 = i * s.G;
-    if (r < s.nx) {
-        for (int c = 0; c < s.nx; c++) fin = fin && is_fin(s.ab[ab_index(S, slot0, c) + r]);
-        for (int c = 0; c < s.nu; c++) fin = fin && is_fin(s.ab[ab_index(S, slot0, s.G + c) + r]);
-    }
-    for (int c = 0; c < s.nx + s.nu; c++)
-        for (int j = r; j < s.ny; j += P) fin = fin && is_fin(s.cd[cd_index(n, i, s.ny, j, c)]);
-    return fin;
-}
-
 template <int P>
 __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
     constexpr int NVP = P < FB_CONNECT_NV_MAX ? P : FB_CONNECT_NV_MAX, NW = CN_NW_MAX;
@@ -75,8 +61,8 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
     const int64_t cpitch = n * nyp, ccpitch = n * a.c.ny;
 
     // ---- every entry of the sources
-    bool fin = side_finite<P>(a.p, n, i, r);
-    if (nxc > 0) fin = fin && side_finite<P>(a.c, n, i, r);
+    bool fin = model_finite<P>(a.p.ab, a.p.cd, nxp, nup, nyp, a.p.G, n, i, r);
+    if (nxc > 0) fin = fin && model_finite<P>(a.c.ab, a.c.cd, nxc, nuc, a.c.ny, a.c.G, n, i, r);
 
     // ---- this lane's row of [I - F D_jz | F C_jz | G]
     const bool live = r < nv;
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
         }
     }
 
-    // ---- [I | M | Nw] by Gauss-Jordan elimination; the column of a step is not kept (it would be a unit vector)
+    // ---- [I | M | Nw] by Gauss-Jordan elimination: fbg::gj_solve's loop with rhs = [m | gw], mirrored by hand (see the head of this file)
     bool used = !live, ok = true;
     int myk = 0;
 #pragma unroll
@@ -167,9 +153,8 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
     }
     panel_sync();
 
-    // ---- the system's status: non-finite input first, then the pivots
-    const bool notfin = g.any(!fin);
-    const int32_t status = notfin ? FB_CONNECT_NOT_FINITE : (g.any(!ok) ? FB_CONNECT_ILL_POSED : 0);
+    // ---- the system's status (the pivots' sizes are not kept: no rpiv is stored)
+    const int32_t status = verdict<P>(g, fin, Solve{ok, 1.0, 1.0}, FB_CONNECT_NOT_FINITE, FB_CONNECT_ILL_POSED).status;
     const bool good = status == 0;
     const double nan = __builtin_nan("");
     if (valid && r == 0 && a.status) a.status[i] = status;
@@ -200,10 +185,10 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
         if (valid) {
 #pragma unroll
             for (int c = 0; c < P; c++)
-                if (c < nx) a.AB[((int64_t)r + (int64_t)nx * c) * n + i] = good ? ar[c] : nan;
+                if (c < nx) a.AB[staged_index(n, i, nx, r, c)] = good ? ar[c] : nan;
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nw) a.AB[((int64_t)r + (int64_t)nx * (nx + c)) * n + i] = good ? br[c] : nan;
+                if (c < nw) a.AB[staged_index(n, i, nx, r, nx + c)] = good ? br[c] : nan;
         }
     }
 
@@ -234,10 +219,10 @@ __global__ __launch_bounds__(CN_WAVE) void k_connect(ConnectArgs a) {
         if (valid) {
 #pragma unroll
             for (int c = 0; c < P; c++)
-                if (c < nx) a.CD[((int64_t)j + (int64_t)ny * c) * n + i] = good ? cr[c] : nan;
+                if (c < nx) a.CD[staged_index(n, i, ny, j, c)] = good ? cr[c] : nan;
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nw) a.CD[((int64_t)j + (int64_t)ny * (nx + c)) * n + i] = good ? dr[c] : nan;
+                if (c < nw) a.CD[staged_index(n, i, ny, j, nx + c)] = good ? dr[c] : nan;
         }
     }
 }

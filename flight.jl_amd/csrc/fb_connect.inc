@@ -36,17 +36,13 @@ int32_t fb_lss_connect(fb_handle p, fb_handle c, const int32_t* jz, int32_t nf, 
         ny = nz;
     }
     if (ny < 1 || ny > fbl::LSS_NY_MAX) return fail("fb_lss_connect: ny = %d, the new model takes 1 <= ny <= %d outputs", (int)ny, fbl::LSS_NY_MAX);
-    for (int k = 0; k < nf; k++)
-        if (jz[k] < 0 || jz[k] >= nz) return fail("fb_lss_connect: jz[%d] = %d is outside [0, %d)", k, (int)jz[k], nz);
-    for (int k = 0; iz && k < ny; k++)
-        if (iz[k] < 0 || iz[k] >= nz) return fail("fb_lss_connect: iz[%d] = %d is outside [0, %d)", k, (int)iz[k], nz);
+    if (!lists_in_range("fb_lss_connect", jz, nf, nz, "jz") || !lists_in_range("fb_lss_connect", iz, ny, nz, "iz")) return -1;
 
     HIPCHK(hipSetDevice(p->device));
     const int64_t n = p->n;
     const size_t un = (size_t)n;
-    const int nc = nx + nw, nwy = nw > ny ? nw : ny, nzero = nx > nwy ? nx : nwy;
     const size_t szF = (size_t)nv * nf * (f_per_system ? un : 1), szG = (size_t)nv * nw * (g_per_system ? un : 1);
-    const size_t szAB = (size_t)nx * nc * un, szCD = (size_t)ny * nc * un, szZ = (size_t)nzero * un;
+    const Staged staged(nx, nw, ny, n);
     std::vector<int32_t> idx(jz, jz + nf);
     for (int k = 0; k < ny; k++) idx.push_back(iz ? iz[k] : k);
     NewHandle made;   // (destroyed on every failing path below, after the blocks are freed)
@@ -54,34 +50,25 @@ int32_t fb_lss_connect(fb_handle p, fb_handle c, const int32_t* jz, int32_t nf, 
     double* d = nullptr;
     int32_t* di = nullptr;
     if (c) HIPCHK(hipStreamSynchronize(c->stream));   // (the compensator's model, should its stream still be writing it)
-    if (int32_t rc = blocks.alloc(&d, szF + szG + szAB + szCD + szZ)) return rc;
+    if (int32_t rc = blocks.alloc(&d, szF + szG + staged.doubles)) return rc;
     if (int32_t rc = blocks.alloc(&di, idx.size() + un)) return rc;
     if (int32_t rc = lss_new_handle(nx, nw, ny, n, p->device, &made.h)) return rc;
-    const fb_handle h = made.h;
-    double *dF = d, *dG = dF + szF, *dAB = dG + szG, *dCD = dAB + szAB, *dZ = dCD + szCD;
+    double *dF = d, *dG = dF + szF, *dS = dG + szG;
     HIPCHK(hipMemcpyAsync(dF, F, sizeof(double) * szF, hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(dG, G, sizeof(double) * szG, hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(di, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, p->stream));
-    HIPCHK(hipMemsetAsync(dZ, 0, sizeof(double) * szZ, p->stream));
+    HIPCHK(hipMemsetAsync(dS, 0, sizeof(double) * staged.AB, p->stream));   // deviation coordinates: xdot0, x0, u0, y0 are zero
     fbc::ConnectArgs a = {};
     a.p = {Lp->ab, Lp->cd, nxp, nup, nyp, Lp->G};
     if (c) a.c = {Lc->ab, Lc->cd, nxc, nuc, nyc, Lc->G};
     a.jz = di; a.iz = di + nf;
     a.F = dF; a.f_e = f_per_system ? n : 1; a.f_s = f_per_system ? 1 : 0;
     a.G = dG; a.g_e = g_per_system ? n : 1; a.g_s = g_per_system ? 1 : 0;
-    a.AB = dAB; a.CD = dCD; a.status = di + idx.size();
+    a.AB = dS + staged.AB; a.CD = dS + staged.CD; a.status = di + idx.size();
     a.n = n; a.nf = nf; a.nw = nw; a.ny = ny;
     if (int32_t rc = family_launch(p, group_for(nx > nv ? nx : nv), n, a, [](auto P) { return fbc::k_connect<P.value>; })) return rc;
     if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));   // (the staging block the new handle's stream is about to read)
-    fbl::LssSrc s;
-    s.xdot0 = s.x0 = s.u0 = s.y0 = dZ;          // deviation coordinates: every offset is zero
-    s.AB = dAB; s.CD = dCD; s.snx = nx; s.snu = nw; s.sny = ny; s.idx = nullptr;
-    if (int32_t rc = lss_gather(h, s, nullptr, nullptr, nullptr)) return rc;
-    h->params.dt = p->params.dt;
-    if (p->stream != p->own_stream) h->stream = p->stream;   // (fb_lss_from_linearization's rule)
-    *out = made.release();
-    return 0;
+    return lss_adopt(p, made, staged.src(dS), nullptr, nullptr, nullptr, out);
 }
 
 }  // extern "C"

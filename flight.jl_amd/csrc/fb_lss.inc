@@ -72,6 +72,24 @@ static int32_t verb_model(const char* verb, fb_handle h) {
 // the model's fields of a verb's argument struct from the handle: [A | B] with its sizes; for a verb on a channel also [C | D], nu and ny
 template <class A> static void verb_args_ab(A& a, fb_handle h) { a.ab = h->lss->ab; a.n = h->n; a.nx = h->lss->nx; a.G = h->lss->G; }
 template <class A> static void verb_args(A& a, fb_handle h) { verb_args_ab(a, h); a.cd = h->lss->cd; a.nu = h->lss->nu; a.ny = h->lss->ny; }
+// a list of a verb's arguments against its limit (a NULL list stands for "all of them" and passes); false with the refusal set
+static bool lists_in_range(const char* verb, const int32_t* list, int cnt, int lim, const char* what) {
+    for (int k = 0; list && k < cnt; k++)
+        if (list[k] < 0 || list[k] >= lim) { fail("%s: %s[%d] = %d is outside [0, %d)", verb, what, k, (int)list[k], lim); return false; }
+    return true;
+}
+// a staged model of n systems on the host (the layout: fbg::staged_index, lss_group.hpp): where its blocks begin, in doubles from its
+// base (xdot0 at 0), what it takes in all, and what k_lss_gather reads of one that lies at `base`
+struct Staged {
+    int nx, nu, ny;
+    size_t x0, u0, y0, AB, CD, doubles;
+    Staged(int nx_, int nu_, int ny_, int64_t n) : nx(nx_), nu(nu_), ny(ny_) {
+        const size_t un = (size_t)n;
+        x0 = nx * un; u0 = x0 + nx * un; y0 = u0 + nu * un; AB = y0 + ny * un; CD = AB + (size_t)nx * (nx + nu) * un;
+        doubles = CD + (size_t)ny * (nx + nu) * un;
+    }
+    fbl::LssSrc src(const double* base) const { return {base, base + x0, base + u0, base + y0, base + AB, base + CD, nx, nu, ny, nullptr}; }
+};
 static int lss_exchange() { const char* e = getenv("FLIGHTBATCH_LSS_EXCHANGE"); return e && !strcmp(e, "shfl") ? 1 : 0; }
 
 static fbl::LssArgs lss_args(fb_handle h) {
@@ -207,7 +225,7 @@ static int32_t lss_unpad(const char* verb, fb_handle h, bool cd, double* M, doub
         double* out = c < nx ? M : N;
         if (!out) continue;
         for (int r = 0; r < rows; r++)
-            for (int64_t i = 0; i < n; i++) out[((int64_t)r + (int64_t)rows * (c < nx ? c : c - nx)) * n + i] = buf[at(L, n, i, r, c)];
+            for (int64_t i = 0; i < n; i++) out[fbg::staged_index(n, i, rows, r, c < nx ? c : c - nx)] = buf[at(L, n, i, r, c)];
     }
     return 0;
 }
@@ -236,6 +254,18 @@ static int32_t lss_new_handle(int32_t nx, int32_t nu, int32_t ny, int64_t n, int
     *out = made.release();
     return 0;
 }
+// The tail of every verb that makes a handle from a staged model `s` on src's device (src: the vehicle handle that was linearised, the
+// plant, the model that was transformed): `made`, from lss_new_handle, gets its copy of the model through the index lists (host, checked
+// by the caller) once src's stream has written `s`, takes src's dt, and is handed over. A source that runs on its caller's stream: so
+// does the model made from it.
+static int32_t lss_adopt(fb_handle src, NewHandle& made, const fbl::LssSrc& s, const int32_t* ix, const int32_t* iu, const int32_t* iy, fb_handle* out) {
+    HIPCHK(hipStreamSynchronize(src->stream));   // (the staged model the new handle's stream is about to read; the verb's copies to the host)
+    if (int32_t rc = lss_gather(made.h, s, ix, iu, iy)) return rc;
+    made.h->params.dt = src->params.dt;
+    if (src->stream != src->own_stream) made.h->stream = src->stream;
+    *out = made.release();
+    return 0;
+}
 
 extern "C" {
 
@@ -257,24 +287,22 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
     if (!xdot0 || !x0 || !u0 || !y0 || !A || !B || !C || !D) return fail("fb_lss_set_model: every block of the model is required");
     HIPCHK(hipSetDevice(h->device));
     const LssState* L = h->lss;
-    const int64_t n = h->n, nx = L->nx, nu = L->nu, ny = L->ny, nc = nx + nu;
+    const int64_t n = h->n, nx = L->nx, nu = L->nu, ny = L->ny;
     // staged on the device in the layout fb_linearize writes, then k_lss_gather with every index: one path for both ways in
+    const Staged staged(L->nx, L->nu, L->ny, n);
     DevBlocks blocks;
     double* st = nullptr;
-    if (int32_t rc = blocks.alloc(&st, (size_t)(2 * nx + nu + ny + (nx + ny) * nc) * n)) return rc;
-    fbl::LssSrc s;
+    if (int32_t rc = blocks.alloc(&st, staged.doubles)) return rc;
     double* p = st;
     int32_t rc = 0;
-    auto put = [&](const double* host, int64_t rows) -> const double* {
-        double* at = p;
-        if (!rc && hipMemcpyAsync(at, host, sizeof(double) * rows * n, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail("fb_lss_set_model: copying the model to the device failed");
+    auto put = [&](const double* host, int64_t rows) {   // (the blocks in the staged order: B behind A, D behind C)
+        if (!rc && hipMemcpyAsync(p, host, sizeof(double) * rows * n, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail("fb_lss_set_model: copying the model to the device failed");
         p += rows * n;
-        return at;
     };
-    s.xdot0 = put(xdot0, nx); s.x0 = put(x0, nx); s.u0 = put(u0, nu); s.y0 = put(y0, ny);
-    s.AB = put(A, nx * nx); put(B, nx * nu);
-    s.CD = put(C, ny * nx); put(D, ny * nu);
-    s.snx = (int)nx; s.snu = (int)nu; s.sny = (int)ny; s.idx = nullptr;
+    put(xdot0, nx); put(x0, nx); put(u0, nu); put(y0, ny);
+    put(A, nx * nx); put(B, nx * nu);
+    put(C, ny * nx); put(D, ny * nu);
+    const fbl::LssSrc s = staged.src(st);
     if (!rc) rc = lss_gather(h, s, nullptr, nullptr, nullptr);
     (void)hipStreamSynchronize(h->stream);
     return rc;
@@ -311,20 +339,9 @@ int32_t fb_lss_from_linearization(fb_handle src, const int32_t* ix, int32_t nx, 
     };
     if (!in_range(ix, nx, snx, "state") || !in_range(iu, nu, snu, "input") || !in_range(iy, ny, sny, "output")) return -1;
     HIPCHK(hipSetDevice(src->device));
-    HIPCHK(hipStreamSynchronize(src->stream));   // (the result the new handle's stream is about to read)
     NewHandle made;
     if (int32_t rc = lss_new_handle(nx, nu, ny, src->n, src->device, &made.h)) return rc;
-    const fb_handle h = made.h;
-    const int64_t n = src->n;
-    fbl::LssSrc s;
-    s.xdot0 = src->lin_buf; s.x0 = s.xdot0 + (int64_t)snx * n; s.u0 = s.x0 + (int64_t)snx * n; s.y0 = s.u0 + (int64_t)snu * n;
-    s.AB = s.y0 + (int64_t)sny * n; s.CD = s.AB + (int64_t)snx * (snx + snu) * n;   // (lin_run's rows)
-    s.snx = snx; s.snu = snu; s.sny = sny; s.idx = nullptr;
-    if (int32_t rc = lss_gather(h, s, ix, iu, iy)) return rc;
-    h->params.dt = src->params.dt;
-    if (src->stream != src->own_stream) h->stream = src->stream;   // (a source that runs on its caller's stream: so does the model made from it)
-    *out = made.release();
-    return 0;
+    return lss_adopt(src, made, Staged(snx, snu, sny, src->n).src(src->lin_buf), ix, iu, iy, out);   // (lin_buf: lin_run's rows)
 }
 
 }  // extern "C"

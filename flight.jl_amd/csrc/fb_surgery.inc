@@ -6,12 +6,6 @@
 // fb_timing_begin_per_launch on the source stamps them); the new handle's copy of the model is then written by k_lss_gather through the
 // subsystem lists, like fb_lss_from_linearization's.
 
-static bool surgery_in_range(const char* verb, const int32_t* list, int cnt, int lim, const char* what) {
-    for (int k = 0; list && k < cnt; k++)
-        if (list[k] < 0 || list[k] >= lim) { fail("%s: %s[%d] = %d is outside [0, %d)", verb, what, k, (int)list[k], lim); return false; }
-    return true;
-}
-
 extern "C" {
 
 int32_t fb_lss_transform(fb_handle src, const int32_t* rows, const int32_t* xdot_zero, const int32_t* ix, int32_t nxo, const int32_t* iu, int32_t nuo,
@@ -29,27 +23,25 @@ int32_t fb_lss_transform(fb_handle src, const int32_t* rows, const int32_t* xdot
     if (nxo < 1 || nxo > nx) return fail("fb_lss_transform: nxo = %d, the new model takes 1 <= nxo <= %d of the source's states", (int)nxo, nx);
     if (nuo < 1 || nuo > nu) return fail("fb_lss_transform: nuo = %d, the new model takes 1 <= nuo <= %d of the source's inputs", (int)nuo, nu);
     if (nyo < 1 || nyo > ny) return fail("fb_lss_transform: nyo = %d, the new model takes 1 <= nyo <= %d of the source's outputs", (int)nyo, ny);
-    if (!surgery_in_range(verb, rows, nx, ny, "rows") || !surgery_in_range(verb, ix, nxo, nx, "ix") || !surgery_in_range(verb, iu, nuo, nu, "iu") ||
-        !surgery_in_range(verb, iy, nyo, ny, "iy")) return -1;
+    if (!lists_in_range(verb, rows, nx, ny, "rows") || !lists_in_range(verb, ix, nxo, nx, "ix") || !lists_in_range(verb, iu, nuo, nu, "iu") ||
+        !lists_in_range(verb, iy, nyo, ny, "iy")) return -1;
 
     HIPCHK(hipSetDevice(src->device));
     const int64_t n = src->n;
     const size_t un = (size_t)n;
-    const int nc = nx + nu;
-    const size_t szV = (size_t)(2 * nx + nu + ny) * un, szAB = (size_t)nx * nc * un, szCD = (size_t)ny * nc * un;
+    const Staged staged(nx, nu, ny, n);
     NewHandle made;   // (destroyed on every failing path below, after the blocks are freed)
     DevBlocks blocks;
     double* d = nullptr;
     int32_t* di = nullptr;
-    if (int32_t rc = blocks.alloc(&d, szV + szAB + szCD + un)) return rc;
+    if (int32_t rc = blocks.alloc(&d, staged.doubles + un)) return rc;
     if (int32_t rc = blocks.alloc(&di, (size_t)nx + un)) return rc;
     if (int32_t rc = lss_new_handle(nxo, nuo, nyo, n, src->device, &made.h)) return rc;
-    const fb_handle h = made.h;
     fbm::TransformArgs a = {};
     verb_args(a, src);
     a.xs = L->xs; a.u0 = L->u0; a.y0 = L->y0;
-    a.xdot0 = d; a.x0 = a.xdot0 + (size_t)nx * un; a.u0_out = a.x0 + (size_t)nx * un; a.y0_out = a.u0_out + (size_t)nu * un;
-    a.AB = d + szV; a.CD = a.AB + szAB; a.rpiv = a.CD + szCD;
+    a.xdot0 = d; a.x0 = d + staged.x0; a.u0_out = d + staged.u0; a.y0_out = d + staged.y0;
+    a.AB = d + staged.AB; a.CD = d + staged.CD; a.rpiv = d + staged.doubles;
     a.status = di + nx;
     if (rows) {
         HIPCHK(hipMemcpyAsync(di, rows, sizeof(int32_t) * nx, hipMemcpyHostToDevice, src->stream));
@@ -60,15 +52,7 @@ int32_t fb_lss_transform(fb_handle src, const int32_t* rows, const int32_t* xdot
     if (int32_t rc = family_launch(src, group_for(nx), n, a, [](auto P) { return fbm::k_transform<P.value>; })) return rc;
     if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, src->stream));
     if (rpiv) HIPCHK(hipMemcpyAsync(rpiv, a.rpiv, sizeof(double) * un, hipMemcpyDeviceToHost, src->stream));
-    HIPCHK(hipStreamSynchronize(src->stream));   // (the staging block the new handle's stream is about to read)
-    fbl::LssSrc s;
-    s.xdot0 = a.xdot0; s.x0 = a.x0; s.u0 = a.u0_out; s.y0 = a.y0_out;
-    s.AB = a.AB; s.CD = a.CD; s.snx = nx; s.snu = nu; s.sny = ny; s.idx = nullptr;
-    if (int32_t rc = lss_gather(h, s, ix, iu, iy)) return rc;
-    h->params.dt = src->params.dt;
-    if (src->stream != src->own_stream) h->stream = src->stream;   // (fb_lss_from_linearization's rule)
-    *out = made.release();
-    return 0;
+    return lss_adopt(src, made, staged.src(d), ix, iu, iy, out);
 }
 
 int32_t fb_lss_steady(fb_handle h, const int32_t* iz, int32_t nz, const double* K, int32_t k_per_system, double* X, double* U, double* K_fwd,
@@ -81,7 +65,7 @@ int32_t fb_lss_steady(fb_handle h, const int32_t* iz, int32_t nz, const double* 
     if (nx + nu > FB_SURGERY_N_MAX) return fail("fb_lss_steady: nx + nu = %d exceeds FB_SURGERY_N_MAX = %d", nx + nu, (int)FB_SURGERY_N_MAX);
     if (nz != nu) return fail("fb_lss_steady: nz = %d, the map takes as many output rows as the model has inputs (nu = %d)", (int)nz, nu);
     if (!iz) return fail("fb_lss_steady: iz is required");
-    if (!surgery_in_range(verb, iz, nz, ny, "iz")) return -1;
+    if (!lists_in_range(verb, iz, nz, ny, "iz")) return -1;
     if (K_fwd && !K) return fail("fb_lss_steady: K_fwd = U + K X needs K");
 
     HIPCHK(hipSetDevice(h->device));

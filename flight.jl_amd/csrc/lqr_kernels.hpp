@@ -289,10 +289,10 @@ __global__ __launch_bounds__(LQR_WAVE) void k_lqr(LqrArgs a) {
         if (a.X) {
 #pragma unroll
             for (int c = 0; c < h; c++)
-                if (c < nx) a.X[((int64_t)r + (int64_t)nx * c) * a.n + i] = good ? x[c] : nan;
+                if (c < nx) a.X[staged_index(a.n, i, nx, r, c)] = good ? x[c] : nan;
         }
         if (a.K) {
-            for (int b = 0; b < nu; b++) a.K[((int64_t)b + (int64_t)nu * r) * a.n + i] = good ? g.kb[b * h + r] : nan;
+            for (int b = 0; b < nu; b++) a.K[staged_index(a.n, i, nu, b, r)] = good ? g.kb[b * h + r] : nan;
         }
     }
     if (r == 0) {

@@ -118,9 +118,9 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_gather(LssSrc s, LssDst d) {
         d.xs[S + slot] = x0;
         if (live) d.x[(int64_t)r * n + i] = x0;
         for (int c = 0; c < G; c++)
-            d.ab[fbg::ab_index(S, slot, c)] = (live && c < d.nx) ? s.AB[((int64_t)sr + (int64_t)s.snx * ix[c]) * n + i] : 0.0;
+            d.ab[fbg::ab_index(S, slot, c)] = (live && c < d.nx) ? s.AB[fbg::staged_index(n, i, s.snx, sr, ix[c])] : 0.0;
         for (int c = 0; c < d.nu; c++)
-            d.ab[fbg::ab_index(S, slot, G + c)] = live ? s.AB[((int64_t)sr + (int64_t)s.snx * (s.snx + iu[c])) * n + i] : 0.0;
+            d.ab[fbg::ab_index(S, slot, G + c)] = live ? s.AB[fbg::staged_index(n, i, s.snx, sr, s.snx + iu[c])] : 0.0;
     }
     for (int c = 0; c < d.nu; c++) {
         const double u0 = s.u0[(int64_t)iu[c] * n + i];
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_gather(LssSrc s, LssDst d) {
         d.y0[(int64_t)j * n + i] = s.y0[(int64_t)sj * n + i];
         for (int c = 0; c < d.nx + d.nu; c++) {
             const int sc = c < d.nx ? ix[c] : s.snx + iu[c - d.nx];
-            d.cd[fbg::cd_index(n, i, d.ny, j, c)] = s.CD[((int64_t)sj + (int64_t)s.sny * sc) * n + i];
+            d.cd[fbg::cd_index(n, i, d.ny, j, c)] = s.CD[fbg::staged_index(n, i, s.sny, sj, sc)];
         }
     }
 }

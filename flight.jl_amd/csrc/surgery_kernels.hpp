@@ -5,10 +5,9 @@
 //   k_transform  T = C[rows, :];  A' = T A inv(T), B' = T B, C' = C inv(T), D' = D, xdot0' = T xdot0 (masked entries exactly 0), x0' = y0[rows]
 //   k_steady     L = [A B; C[iz, :] D[iz, :]];  L [X; U] = [0; I];  K_fwd = U + K X
 // One system per group of P lanes of one wave (P = 8, 16 or 32, the smallest with a lane per row of T or of L; 64 / P systems per wave,
-// one wave per workgroup). Lane r owns row r as register arrays; Gauss-Jordan elimination on the augmented rows ([T | I], [L | 0; I])
-// with the family's pivot rule (fbg::Lanes::pivot, lss_group.hpp), every step a compile-time k, the steps k >= the system's size behind a
-// wave-uniform branch. The rows stay with their lanes: the lane that was the pivot of step k ends with row k of the solution and puts
-// it at row k of the group's LDS panel, from where every product reads it back as broadcasts. Every sum starts from its first term's
+// one wave per workgroup). Lane r owns row r of the augmented rows ([T | I], [L | 0; I]) as an fbg::Row; the family's solve
+// (fbg::gj_solve, lss_group.hpp: Gauss-Jordan elimination, the rows staying with their lanes) puts row k of the solution
+// at row k of the group's LDS panel, from where every product reads it back as broadcasts. Every sum starts from its first term's
 // accumulator (0, or U for K_fwd) and runs with k ascending as explicit fma, so a result is a function of the system's own values
 // only. The panel belongs to one wave: fences and wave_barrier, no s_barrier. Lanes past the batch's end work on the last system
 // again and store nothing. k_transform's result goes to a staging block in fb_linearize's layout; fbl::k_lss_gather makes the new
@@ -46,21 +45,12 @@ struct SteadyArgs {
     int32_t* status; double* rpiv;
 };
 
-// the smallest pivot magnitude over the largest of a system's elimination, and its status word
-struct Verdict { int32_t status; double rpiv; };
-template <int P>
-__device__ inline Verdict verdict(const fbg::Lanes<P>& g, bool fin, bool ok, double pmin, double pmax) {
-    if (g.any(!fin)) return {FB_SURGERY_NOT_FINITE, __builtin_nan("")};
-    if (g.any(!ok)) return {FB_SURGERY_SINGULAR, 0.0};
-    return {0, pmin / pmax};
-}
-
 template <int P>
 __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
     constexpr int NW = SG_NU_MAX, LD = P + NW + 1, NG = SG_WAVE / P, ROW = 2 * P, GRP = ROW + P * LD;   // (ROW and GRP are even: 16-byte rows)
     __shared__ __attribute__((aligned(16))) double lds[NG * GRP];
     const fbg::Lanes<P> g;
-    double* prow = lds + (threadIdx.x / P) * GRP;   // the scaled pivot row of the current step: t | v
+    double* prow = lds + (threadIdx.x / P) * GRP;   // the scaled pivot row of the current step: e | rhs
     double* sol = prow + ROW;                       // inv(T), then [A inv(T) | B | xdot0]: P x LD
     const int r = g.r;
     const int nx = a.nx, nu = a.nu, ny = a.ny;
@@ -84,13 +74,13 @@ __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
     if (!a.rows) {
         if (!valid) return;
         if (live) {
-            for (int c = 0; c < nx; c++) a.AB[((int64_t)r + (int64_t)nx * c) * n + i] = a.ab[ab_index(S, slot0, c) + r];
-            for (int c = 0; c < nu; c++) a.AB[((int64_t)r + (int64_t)nx * (nx + c)) * n + i] = a.ab[ab_index(S, slot0, a.G + c) + r];
+            for (int c = 0; c < nx; c++) a.AB[staged_index(n, i, nx, r, c)] = a.ab[ab_index(S, slot0, c) + r];
+            for (int c = 0; c < nu; c++) a.AB[staged_index(n, i, nx, r, nx + c)] = a.ab[ab_index(S, slot0, a.G + c) + r];
             a.xdot0[(int64_t)r * n + i] = zeroed ? 0.0 : a.xs[slot0 + r];
             a.x0[(int64_t)r * n + i] = a.xs[S + slot0 + r];
         }
         for (int j = r; j < ny; j += P)
-            for (int c = 0; c < nx + nu; c++) a.CD[((int64_t)j + (int64_t)ny * c) * n + i] = cdp[(int64_t)c * cpitch + j];
+            for (int c = 0; c < nx + nu; c++) a.CD[staged_index(n, i, ny, j, c)] = cdp[(int64_t)c * cpitch + j];
         if (r == 0) {
             if (a.status) a.status[i] = 0;
             if (a.rpiv) a.rpiv[i] = 1.0;
@@ -99,68 +89,23 @@ __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
     }
 
     // ---- every entry of the source that the new model is made of
-    bool fin = true;
-    if (live) {
-        for (int c = 0; c < nx; c++) fin = fin && is_fin(a.ab[ab_index(S, slot0, c) + r]);
-        for (int c = 0; c < nu; c++) fin = fin && is_fin(a.ab[ab_index(S, slot0, a.G + c) + r]);
-        fin = fin && is_fin(a.xs[slot0 + r]);
-    }
-    for (int c = 0; c < nx + nu; c++)
-        for (int j = r; j < ny; j += P) fin = fin && is_fin(cdp[(int64_t)c * cpitch + j]);
+    bool fin = model_finite<P>(a.ab, a.cd, nx, nu, ny, a.G, n, i, r);
+    if (live) fin = fin && is_fin(a.xs[slot0 + r]);
 
     // ---- this lane's row of [T | I]
     const int z = live ? a.rows[r] : 0;
-    double t[P], v[P];
+    Row<P, P> tv;                                   // e: T, rhs: I
 #pragma unroll
     for (int c = 0; c < P; c++) {
-        t[c] = (live && c < nx) ? cdp[(int64_t)c * cpitch + z] : 0.0;
-        v[c] = (live && c == r) ? 1.0 : 0.0;
+        tv.e[c] = (live && c < nx) ? cdp[(int64_t)c * cpitch + z] : 0.0;
+        tv.rhs[c] = (live && c == r) ? 1.0 : 0.0;
     }
 
-    // ---- [. | inv(T)] by Gauss-Jordan elimination; the column of a step is not kept (it would be a unit vector)
-    bool used = !live, ok = true;
-    int myk = 0;
-    double pmin = DBL_MAX, pmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < P; k++) {
-        if (k < nx) {
-            const fbg::Pivot pv = g.pivot(used, used ? -1.0 : fabs(t[k]), k);
-            ok = ok && pv.found;
-            pmin = fmin(pmin, pv.m);
-            pmax = fmax(pmax, pv.m);
-            panel_sync();
-            if (r == pv.p) {
-                const double ip = 1.0 / t[k];
-#pragma unroll
-                for (int j = k + 1; j < P; j++) { t[j] *= ip; prow[j] = t[j]; }
-#pragma unroll
-                for (int j = 0; j < P; j++) { v[j] *= ip; prow[P + j] = v[j]; }
-                used = true; myk = k;
-            }
-            panel_sync();
-            if (live && r != pv.p) {
-                const double f = t[k];
-#pragma unroll
-                for (int j = k + 1; j < P; j++) t[j] = fma(-f, prow[j], t[j]);
-                const double2* row = reinterpret_cast<const double2*>(prow + P);
-#pragma unroll
-                for (int j = 0; j < P; j += 2) {
-                    const double2 s = row[j / 2];
-                    v[j] = fma(-f, s.x, v[j]);
-                    v[j + 1] = fma(-f, s.y, v[j + 1]);
-                }
-            }
-        }
-    }
-    panel_sync();
-    if (live) {
-#pragma unroll
-        for (int j = 0; j < P; j++) sol[myk * LD + j] = v[j];
-    }
-    panel_sync();
+    // ---- [. | inv(T)]: row k of inv(T) at row k of sol
+    const Solve sv = gj_solve<P, LD>(g, tv, prow, sol, live, nx);
 
-    // ---- the system's status: non-finite input first, then the pivots
-    const Verdict vd = verdict<P>(g, fin, ok, pmin, pmax);
+    // ---- the system's status
+    const Verdict vd = verdict<P>(g, fin, sv, FB_SURGERY_NOT_FINITE, FB_SURGERY_SINGULAR);
     const bool good = vd.status == 0;
     const double nan = __builtin_nan("");
     if (valid && r == 0) {
@@ -182,8 +127,8 @@ __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
         if (valid) {
 #pragma unroll
             for (int c = 0; c < P; c++)
-                if (c < nx) a.CD[((int64_t)j + (int64_t)ny * c) * n + i] = good ? cr[c] : nan;
-            for (int c = 0; c < nu; c++) a.CD[((int64_t)j + (int64_t)ny * (nx + c)) * n + i] = good ? cdp[(int64_t)(nx + c) * cpitch + j] : nan;
+                if (c < nx) a.CD[staged_index(n, i, ny, j, c)] = good ? cr[c] : nan;
+            for (int c = 0; c < nu; c++) a.CD[staged_index(n, i, ny, j, nx + c)] = good ? cdp[(int64_t)(nx + c) * cpitch + j] : nan;
         }
     }
 
@@ -223,10 +168,10 @@ __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
         if (valid) {
 #pragma unroll
             for (int c = 0; c < P; c++)
-                if (c < nx) a.AB[((int64_t)r + (int64_t)nx * c) * n + i] = good ? o[c] : nan;
+                if (c < nx) a.AB[staged_index(n, i, nx, r, c)] = good ? o[c] : nan;
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nu) a.AB[((int64_t)r + (int64_t)nx * (nx + c)) * n + i] = good ? o[P + c] : nan;
+                if (c < nu) a.AB[staged_index(n, i, nx, r, nx + c)] = good ? o[P + c] : nan;
             a.xdot0[(int64_t)r * n + i] = good ? (zeroed ? 0.0 : o[P + NW]) : nan;
             a.x0[(int64_t)r * n + i] = a.y0[(int64_t)z * n + i];
         }
@@ -238,7 +183,7 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
     constexpr int NW = SG_NU_MAX, LD = NW + 1, NG = SG_WAVE / P, ROW = P + NW, GRP = ROW + P * LD;   // (ROW and GRP are even: 16-byte rows)
     __shared__ __attribute__((aligned(16))) double lds[NG * GRP];
     const fbg::Lanes<P> g;
-    double* prow = lds + (threadIdx.x / P) * GRP;   // the scaled pivot row of the current step: l | rh
+    double* prow = lds + (threadIdx.x / P) * GRP;   // the scaled pivot row of the current step: e | rhs
     double* sol = prow + ROW;                       // [X; U], P x LD
     const int r = g.r;
     const int nx = a.nx, nu = a.nu, ny = a.ny, m = nx + nu;
@@ -254,62 +199,23 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
     const double* src = top ? a.ab + slot0 + r : a.cd + cd_index(n, i, ny, z, 0);
     const int64_t pitch = top ? S : n * ny;
     bool fin = true;
-    double l[P], rh[NW];
+    Row<P, NW> lr;                                  // e: L, rhs: [0; I]
 #pragma unroll
     for (int c = 0; c < P; c++) {
         double e = 0.0;
         if (live && c < m) e = src[(int64_t)((top && c >= nx) ? a.G + c - nx : c) * pitch];
         fin = fin && is_fin(e);
-        l[c] = e;
+        lr.e[c] = e;
     }
 #pragma unroll
-    for (int c = 0; c < NW; c++) rh[c] = (live && r == nx + c) ? 1.0 : 0.0;
+    for (int c = 0; c < NW; c++) lr.rhs[c] = (live && r == nx + c) ? 1.0 : 0.0;
     if (a.K && r < nu)
         for (int k = 0; k < nx; k++) fin = fin && is_fin(a.K[((int64_t)r + (int64_t)nu * k) * a.k_e + i * a.k_s]);
 
-    // ---- [. | X; U] by Gauss-Jordan elimination
-    bool used = !live, ok = true;
-    int myk = 0;
-    double pmin = DBL_MAX, pmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < P; k++) {
-        if (k < m) {
-            const fbg::Pivot pv = g.pivot(used, used ? -1.0 : fabs(l[k]), k);
-            ok = ok && pv.found;
-            pmin = fmin(pmin, pv.m);
-            pmax = fmax(pmax, pv.m);
-            panel_sync();
-            if (r == pv.p) {
-                const double ip = 1.0 / l[k];
-#pragma unroll
-                for (int j = k + 1; j < P; j++) { l[j] *= ip; prow[j] = l[j]; }
-#pragma unroll
-                for (int j = 0; j < NW; j++) { rh[j] *= ip; prow[P + j] = rh[j]; }
-                used = true; myk = k;
-            }
-            panel_sync();
-            if (live && r != pv.p) {
-                const double f = l[k];
-#pragma unroll
-                for (int j = k + 1; j < P; j++) l[j] = fma(-f, prow[j], l[j]);
-                const double2* row = reinterpret_cast<const double2*>(prow + P);
-#pragma unroll
-                for (int j = 0; j < NW; j += 2) {
-                    const double2 s = row[j / 2];
-                    rh[j] = fma(-f, s.x, rh[j]);
-                    rh[j + 1] = fma(-f, s.y, rh[j + 1]);
-                }
-            }
-        }
-    }
-    panel_sync();
-    if (live) {
-#pragma unroll
-        for (int j = 0; j < NW; j++) sol[myk * LD + j] = rh[j];
-    }
-    panel_sync();
+    // ---- [. | X; U]: row k of [X; U] at row k of sol
+    const Solve sv = gj_solve<P, LD>(g, lr, prow, sol, live, m);
 
-    const Verdict vd = verdict<P>(g, fin, ok, pmin, pmax);
+    const Verdict vd = verdict<P>(g, fin, sv, FB_SURGERY_NOT_FINITE, FB_SURGERY_SINGULAR);
     const bool good = vd.status == 0;
     const double nan = __builtin_nan("");
     if (valid && r == 0) {
@@ -324,7 +230,7 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
         if (out) {
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nu) out[((int64_t)ro + (int64_t)rows * c) * n + i] = good ? sol[r * LD + c] : nan;
+                if (c < nu) out[staged_index(n, i, rows, ro, c)] = good ? sol[r * LD + c] : nan;
         }
     }
     // ---- row r of K_fwd = U + K X
@@ -341,7 +247,7 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
         if (valid) {
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nu) a.Kfwd[((int64_t)r + (int64_t)nu * c) * n + i] = good ? acc[c] : nan;
+                if (c < nu) a.Kfwd[staged_index(n, i, nu, r, c)] = good ? acc[c] : nan;
         }
     }
 }

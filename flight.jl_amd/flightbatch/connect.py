@@ -49,14 +49,14 @@ def _rows(entries, labels, what):
     return np.array(out, dtype=np.int32)
 
 
-def _gain(M, n, rows, cols, name):
-    """(flat array, per_system) of a gain given as [rows, cols] for the batch or [N, rows, cols] per system"""
+def _gain(M, n, rows, cols, name, verb="connect"):
+    """(flat array, per_system) of a gain given as [rows, cols] for the batch or [N, rows, cols] per system; verb: whose message a refusal is"""
     M = np.asarray(M, dtype=np.float64)
     if M.shape == (rows, cols):
         return np.ascontiguousarray(M.reshape(-1, order="F")), 0
     if M.shape == (n, rows, cols):
         return pack_matrix(M), 1
-    raise ValueError(f"connect: {name} must be [{rows}, {cols}] or [{n}, {rows}, {cols}], got {M.shape}")
+    raise ValueError(f"{verb}: {name} must be [{rows}, {cols}] or [{n}, {rows}, {cols}], got {M.shape}")
 
 
 def connect(plant: LinearWorld, comp: LinearWorld | None = None, *, feedback, inputs, outputs=None, reads=None, input_labels=None) -> ConnectResult:

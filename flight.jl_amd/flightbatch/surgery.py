@@ -123,10 +123,7 @@ def steady_state(world: LinearWorld, z, K=None) -> SteadyResult:
     iz, _ = _pick(z, world.y_labels, "an output", "steady_state")
     n, nx, nu = world.n, world.nx, world.nu
     nz = len(iz)
-    try:
-        Kf, kper = (None, 0) if K is None else _gain(K, n, nu, nx, "K")
-    except ValueError as e:
-        raise ValueError(str(e).replace("connect:", "steady_state:", 1)) from None
+    Kf, kper = (None, 0) if K is None else _gain(K, n, nu, nx, "K", "steady_state")
     X, U, Kfwd = np.empty(nx * nz * n), np.empty(nu * nz * n), (np.empty(nu * nz * n) if K is not None else None)
     status, rpiv = np.empty(n, dtype=np.int32), np.empty(n)
     check(lib.fb_lss_steady(world._h, _pi(iz), nz, None if Kf is None else _pd(Kf), kper, _pd(X), _pd(U), None if Kfwd is None else _pd(Kfwd),

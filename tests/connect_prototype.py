@@ -1,17 +1,18 @@
 """The algorithm of fb_lss_connect restated in numpy (test infrastructure; kernel: csrc/connect_kernels.hpp; docs/design/linearize.md,
-"Closing loops on the device"), in float64 and in np.longdouble (its own Gauss-Jordan elimination: np.linalg does not take longdouble), and
-the generator of the random cases.
+"Closing loops on the device"), in float64 and in np.longdouble (the family's Gauss-Jordan elimination, surgery_prototype.solve: np.linalg
+does not take longdouble), and the generator of the random cases.
 
     stacked   v = [u_p; u_c], z = [y_p; y_c], x = [x_p; x_c]; A, B, C, D block-diagonal
     rows      W = [I - F D[jz, :] | F C[jz, :] | G], one row per entry of v
-    E         Gauss-Jordan elimination on W with the kernel's pivot rule: the pivot of step k is the not yet used row with the largest
-              |W_ik| (ties: the lowest row), the rows stay where they are; the row that was the pivot of step k ends as row k of [M | Nw]
+    E         [M | Nw] = solve(I - F D[jz, :], [F C[jz, :] | G]), the one numpy statement of the device's solve (fbg::gj_solve)
     result    A' = A + B M, B' = B Nw, C' = C[iz, :] + D[iz, :] M, D' = D[iz, :] Nw
 
 The sums over k run with k ascending, as in the kernel; the products are numpy's matmul (each sum formed first, then added), where the
 kernel starts from the term it adds to and fuses every multiply-add: the two differ by rounding only, which the accuracy rule of
 tests/test_gpu_connect.py allows for. Where F D[jz, :] = 0 every pivot is exactly 1 and M = F C[jz, :], Nw = G to the last bit."""
 import numpy as np
+
+from surgery_prototype import block_dev, solve  # noqa: F401  (block_dev: the tests reach it through this module)
 
 ILL_POSED, NOT_FINITE = 1, 2          # FB_CONNECT_ILL_POSED, FB_CONNECT_NOT_FINITE (include/flightbatch.h)
 NV_MAX, NF_MAX, NZ_MAX = 16, 32, 128
@@ -49,30 +50,6 @@ def stack(p, c, dtype=np.float64):
     return tuple(out)
 
 
-def eliminate(W, nv):
-    """([M | Nw], ok) from W = [I - F D_jz | F C_jz | G] by Gauss-Jordan elimination, the kernel's way"""
-    W = W.copy()
-    used = np.zeros(nv, dtype=bool)
-    sigma = np.zeros(nv, dtype=int)
-    ok = True
-    with np.errstate(all="ignore"):
-        for k in range(nv):
-            v = np.where(used, -1.0, np.abs(W[:, k]))
-            m = np.nan if np.all(np.isnan(v)) else np.nanmax(v)
-            cand = np.flatnonzero(~used & (v == m))
-            if cand.size == 0 or not (m > 0.0) or not np.isfinite(m):
-                ok = False
-            p = int(cand[0]) if cand.size else k
-            ip = 1.0 / W[p, k]
-            row = W[p] * ip
-            f = W[:, k].copy()
-            W = W - np.outer(f, row)
-            W[p] = row
-            used[p] = True
-            sigma[k] = p
-    return W[sigma, nv:], ok
-
-
 def connect(p, c, jz, F, G, iz, dtype=np.float64):
     """(A', B', C', D', status) of one system; a system with a non-zero status has NaN matrices"""
     A, B, C, D = stack(p, c, dtype)
@@ -82,8 +59,7 @@ def connect(p, c, jz, F, G, iz, dtype=np.float64):
     nx, nv = B.shape
     nw = G.shape[1]
     with np.errstate(all="ignore"):
-        W = np.concatenate([np.eye(nv, dtype=dtype) - F @ D[jz], F @ C[jz], G], axis=1)
-        S, ok = eliminate(W, nv)
+        S, ok, _ = solve(np.eye(nv, dtype=dtype) - F @ D[jz], np.concatenate([F @ C[jz], G], axis=1))
         M, Nw = S[:, :nx], S[:, nx:]
         out = (A + B @ M, B @ Nw, C[iz] + D[iz] @ M, D[iz] @ Nw)
     finite = all(np.all(np.isfinite(m)) for m in (A, B, C, D, F, G))
@@ -120,14 +96,6 @@ def case(shape, n=N_SYS, seed=SEED):
         D = stack(tuple(m[i] for m in P), None if Cc is None else tuple(m[i] for m in Cc))[3]
         F[i] *= 0.5 / np.linalg.norm(F[i] @ D[jz], 2)
     return P, Cc, jz, F, mk(n, nv, nw), iz
-
-
-def block_dev(got, want):
-    """the worst |got - want| over a block divided by the block's largest |want|, per system: [N]"""
-    got, want = np.asarray(got), np.asarray(want)
-    n = want.shape[0]
-    d = np.abs(got.astype(np.longdouble) - want).reshape(n, -1).max(axis=1)
-    return (d / np.abs(want).reshape(n, -1).max(axis=1)).astype(np.float64)
 
 
 _SIDES = {}
