@@ -1198,6 +1198,20 @@ template <bool ALWAYS> __device__ __forceinline__ unsigned long long duo_run_mas
 template <int KIN, bool X, bool PERENV> constexpr bool duo_sums_stay() { return duo_r8<KIN, X, PERENV>() && DUO_R8_SUMS_STAY; }
 template <int KIN, bool X, bool PERENV> constexpr bool duo_aero_panel() { return duo_r8<KIN, X, PERENV>() && DUO_R8_AERO_PANEL; }
 template <int KIN, bool X, bool PERENV> using duo_opt = DuoOpt<duo_r8<KIN, X, PERENV>() && DUO_R8_PIN_IN_PLACE>;
+// "Round 9" (docs/design/k_step_duo.md), the same one instance, a constexpr switch per step, kept by measurement (profiles/r09_ab_stage_emit.txt:
+// together the two steps clear the bar for a gain, step A alone stays below it). The values can be given on the compiler's command line, for
+// A/B builds (tools/build_variant.sh TAG -DFB_DUO_R9_P_SUMS_STAY=0).
+#ifndef FB_DUO_R9_STAGE_EMIT
+#define FB_DUO_R9_STAGE_EMIT 1
+#endif
+#ifndef FB_DUO_R9_P_SUMS_STAY
+#define FB_DUO_R9_P_SUMS_STAY 1
+#endif
+constexpr bool DUO_R9_STAGE_EMIT = FB_DUO_R9_STAGE_EMIT;     // step A: stage 3's part of a row's emit behind one scalar branch per emit site (DuoEmit<..., STAGE_EMIT>)
+constexpr bool DUO_R9_P_SUMS_STAY = FB_DUO_R9_P_SUMS_STAY;   // step B: role P's four register-resident stage sums keep their registers through the loop
+template <int KIN, bool X, bool PERENV> constexpr bool duo_r9() { return KIN == FB_KIN_WA && !X && !PERENV; }
+template <int KIN, bool X, bool PERENV> constexpr bool duo_stage_emit() { return duo_r9<KIN, X, PERENV>() && DUO_R9_STAGE_EMIT; }
+template <int KIN, bool X, bool PERENV> constexpr bool duo_p_sums_stay() { return duo_r9<KIN, X, PERENV>() && DUO_R9_P_SUMS_STAY; }
 template <int NK>
 struct DuoK {
     double r[NK];
@@ -1367,7 +1381,11 @@ FBD void duo_wait(DuoSync& sy, int k) {
 #endif
 }
 
-template <int ROLE, bool X = false, int NDL = DUO_ND, bool SUMS_STAY = false>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
+// STAGE_EMIT ("Round 9"): the two forms of a row's emit — stages 0-2, stage 3 — told apart by one scalar branch on `last` per emit site (the stage is
+// wave-uniform), instead of the product with `em` and the 64-bit select on `last` in every row of every evaluation:
+//     stages 0-2 (the fall-through):  acc = fma(eb, k, acc)                  x_stage = fma(ee, k, xs)     (A * 1.0 is A for every A: no bit changes)
+//     stage 3:                        A = fma(eb, k, acc), acc = A * 0.0     x_stage = fma(ee, A, xs)     (a product still: the zero keeps A's sign)
+template <int ROLE, bool X = false, int NDL = DUO_ND, bool SUMS_STAY = false, bool STAGE_EMIT = false>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
 struct DuoEmit {
     static constexpr int role = ROLE;
     static constexpr bool x2 = X;   // the Cessna172Xv2 instance: role D fetches the evaluation's aerodynamic sums behind role P's point R, every publication
@@ -1413,10 +1431,26 @@ struct DuoEmit {
         else if (ROLE == 2 && slot(r) >= NDL) acc_r[slot(r) - NDL] = v;
         else acc_l[slot(r) * DUO_B + t] = v;
     }
+    // one row's stage 3 (STAGE_EMIT), behind the branch: A takes k's place as the state row's increment, and the product that zeroes the sum takes
+    // A's place. (The product first: A is then dead behind the asm statement, and the increment needs no copy of it. The asm statement makes
+    // the increment opaque, which keeps the compiler from turning the branch back into selects.)
+    __device__ __forceinline__ static void stage3(double& A, double& sel) {
+        const double z = A * 0.0;
+        sel = A;
+        asm volatile("" : "+v"(sel));
+        A = z;
+    }
     __device__ __forceinline__ void operator()(int j, double kj) const {
         static_assert(ROLE == 1 || ROLE == 2, "");
         const int r = SV::row(j), idx = r * DUO_B + t;
         const double xs = (ROLE == 1 && !X) ? xn_r[slot(r)] : xs_l[idx];
+        if constexpr (STAGE_EMIT) {
+            double A = __builtin_fma(eb, kj, aget(r)), sel = kj;
+            if (__builtin_expect(last, false)) stage3(A, sel);
+            aset(r, A);
+            xwr_l[idx] = __builtin_fma(ee, sel, xs);
+            return;
+        }
         const double A = __builtin_fma(eb, kj, aget(r));
         aset(r, A * em);
         xwr_l[idx] = __builtin_fma(ee, last ? A : kj, xs);
@@ -1426,6 +1460,22 @@ struct DuoEmit {
         double xs[NE], A[NE];
 #pragma unroll
         for (int e = 0; e < NE; e++) { const int r = SV::row(j0 + e); xs[e] = (ROLE == 1 && !X) ? xn_r[slot(r)] : xs_l[r * DUO_B + t]; A[e] = aget(r); }
+        if constexpr (STAGE_EMIT) {
+            // the reads above, the sums of the batch, then ONE scalar branch that stages 0-2 fall through, the state rows, the writes. What
+            // the two forms share — A = fma(eb, k, acc), x = fma(ee, ·, xs) — stands once, around the branch: stage 3 alone puts A in k's
+            // place and zeroes the sum. (Two whole bodies, `if (last) ... else ...`, compile to a diamond with an edge from the end of one
+            // body into the other: the register-resident sums then stay live through the body that replaces them, and are copied at the join.)
+            double sel[NE];
+#pragma unroll
+            for (int e = 0; e < NE; e++) { A[e] = __builtin_fma(eb, k[e], A[e]); sel[e] = k[e]; }
+            if (__builtin_expect(last, false)) {
+#pragma unroll
+                for (int e = 0; e < NE; e++) stage3(A[e], sel[e]);
+            }
+#pragma unroll
+            for (int e = 0; e < NE; e++) { const int r = SV::row(j0 + e); aset(r, A[e]); xwr_l[r * DUO_B + t] = __builtin_fma(ee, sel[e], xs[e]); }
+            return;
+        }
 #pragma unroll
         for (int e = 0; e < NE; e++) A[e] = __builtin_fma(eb, k[e], A[e]);
 #pragma unroll
@@ -1693,7 +1743,9 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
             const Tables T = {(lds_cptr)lds + lds_off, a.egm96, (lds_cptr)rk + lds_off, (gk_cptr)a.tables + lds_off};
             [[maybe_unused]] const bool tap = X && (c & DUO_C_TAP);
             if constexpr (X) { if (sums_for != stg || (c & DUO_C_CMD)) form_sums(stg, lds_off); }
-            if (__builtin_amdgcn_ballot_w64(run) != 0) {   // (the same in both waves of a pair)
+            // (DUO_R9_P_SUMS_STAY: as in role D below — one divergent region around the evaluation and the "nobody runs" publication behind it, so
+            // that this role's register-resident stage sums pass one join per iteration and keep their registers)
+            if (duo_run_mask<duo_p_sums_stay<KIN, X, PERENV>()>(run) != 0) {   // (the same in both waves of a pair)
                 if (run) {
                     StepAux aux;
                     InputsDuoP inl = in;
@@ -1708,7 +1760,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     }
                     DUO_MARK(1, 12);   // (Cessna172Xv2: stage positions and aerodynamic sums formed and stored)
                     asm volatile("" : "+v"(inl.throttle), "+v"(inl.mixture));
-                    const DuoEmit<1, X> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accp_l, acc_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
+                    const DuoEmit<1, X, DUO_ND, false, duo_stage_emit<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accp_l, acc_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
                                                 tap, i, xn_r};
                     if constexpr (X) {
                         if (tap) {   // what the control laws read of the actuators: the Ranged positions of the state x_{n+1} (InputsX::pos), and the commands this f_ode! saw
@@ -1743,6 +1795,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     }
                 }
             } else duo_publish(sy, DUO_PT_W);   // (an evaluation nobody runs: role D must not wait for it)
+            if constexpr (duo_p_sums_stay<KIN, X, PERENV>()) { if (__builtin_amdgcn_ballot_w64(run) == 0) duo_publish(sy, DUO_PT_W); }
             if constexpr (X) {
                 if (tap) {
                     // f_periodic!(avionics, vehicle), the longitudinal half: role D has run f_step! on x_{n+1} and written the flags (DUO_F_CTL: the
@@ -1918,7 +1971,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     inl.aero_g = ka->duo_pld + il;
                     inl.n = ka->n;
                 }
-                const DuoEmit<2, X, DUO_NDL, duo_sums_stay<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
+                const DuoEmit<2, X, DUO_NDL, duo_sums_stay<KIN, X, PERENV>(), duo_stage_emit<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
                                             tap_now, i};
                 const SV xv = {sk.xrd_l + t + lds_off};
 #if defined(FB_DUO_ONLY) && FB_DUO_ONLY == 1
