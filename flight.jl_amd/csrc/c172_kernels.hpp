@@ -1212,6 +1212,20 @@ constexpr bool DUO_R9_P_SUMS_STAY = FB_DUO_R9_P_SUMS_STAY;   // step B: role P's
 template <int KIN, bool X, bool PERENV> constexpr bool duo_r9() { return KIN == FB_KIN_WA && !X && !PERENV; }
 template <int KIN, bool X, bool PERENV> constexpr bool duo_stage_emit() { return duo_r9<KIN, X, PERENV>() && DUO_R9_STAGE_EMIT; }
 template <int KIN, bool X, bool PERENV> constexpr bool duo_p_sums_stay() { return duo_r9<KIN, X, PERENV>() && DUO_R9_P_SUMS_STAY; }
+// "Round 10" (docs/design/k_step_duo.md), the same one instance: the polls of the pair synchronisation (DuoSync, below) take their target from
+// a scalar register in both roles. The value can be given on the compiler's command line, for A/B builds, as in round 9.
+#ifndef FB_DUO_R10_SCALAR_SYNC
+#define FB_DUO_R10_SCALAR_SYNC 1
+#endif
+#ifndef FB_DUO_R10_PEEL
+#define FB_DUO_R10_PEEL 1
+#endif
+constexpr bool DUO_R10_SCALAR_SYNC = FB_DUO_R10_SCALAR_SYNC;   // step A: the wait's target and loop condition are scalar in role P as in role D
+constexpr bool DUO_R10_PEEL = FB_DUO_R10_PEEL;                 // step A': the pass that finds the count at once is straight-line code, the loop stands out of line
+template <int KIN, bool X, bool PERENV> constexpr bool duo_r10() { return KIN == FB_KIN_WA && !X && !PERENV; }
+template <int KIN, bool X, bool PERENV> constexpr bool duo_scalar_sync() { return duo_r10<KIN, X, PERENV>() && DUO_R10_SCALAR_SYNC; }
+// how a role waits (duo_wait's template arguments in one word: bit 0 SCALAR, bit 1 PEEL)
+template <int KIN, bool X, bool PERENV> constexpr int duo_sync_mode() { return (duo_scalar_sync<KIN, X, PERENV>() ? 1 : 0) | (duo_scalar_sync<KIN, X, PERENV>() && DUO_R10_PEEL ? 2 : 0); }
 template <int NK>
 struct DuoK {
     double r[NK];
@@ -1318,8 +1332,14 @@ struct InputsDuoDX : InputsDuoD {
 // The LDS serves one wave's instructions in order: what a wave wrote ahead of its counter is there when the partner sees the count, and
 // what it read ahead of it has been read. The waits are bounded (a partner that never arrives would hang the GPU): the pair then goes on
 // and its aircraft are flagged FB_ST_NAN when the kernel ends.
+// The poll (duo_wait): one lane-uniform ds_read of the partner's counter, v_readfirstlane, a scalar compare against base + k + 1; a pass that
+// does not find the count sleeps 64 cycles (s_sleep 1) and reads again, at most 2^20 times. Measured (profiles/r10_duo_wait.txt): role D finds
+// the count at its first pass in every wait — its three waits are three LDS round trips on the critical path, about 140 cycles each — while
+// role P fails about 2 passes per evaluation at T and 6 to 12 at X, where it waits for role D to finish. What a wait costs role D is therefore
+// the shape of the pass that SUCCEEDS: a taken branch on the way into or out of it is worth about 0.2 % of the launch per wait site ("Round 10").
 // Diagnostic builds (-DFB_STAMP -DFB_DUO_WAITPROF, tools/duo_waitprof.py): wave 0 (role P) and wave 4 (role D) of workgroup 0 add the
-// cycles they spend in wait k to g_stamp_acc[k] / [8 + k].
+// cycles they spend in wait k to g_stamp_acc[k] / [8 + k], and the passes of the poll that failed to g_stamp_acc[4 + k] / [12 + k]
+// (g_stamp_cnt there: the waits that failed a pass at all).
 #ifdef FB_DUO_SYNC_DEBUG
 __device__ unsigned g_duo_sync_dbg[40];
 #endif
@@ -1348,13 +1368,29 @@ FBD void duo_publish(DuoSync& sy, int k) {
     *sy.mine = sy.base + k + 1;
     asm volatile("" ::: "memory");   // (... and every one below stays below)
 }
+// SCALAR ("Round 10"): `base` is read through v_readfirstlane. It is wave-uniform by construction, but in role P the compiler kept it in a VGPR
+// and built each poll as a loop over EXEC masks (about 19 instructions for a pass that finds the count and 23 for one that does not, against
+// 6 and 7 of the scalar loop that role D had all along).
+// PEEL: the first poll stands ahead of the loop and the loop out of line (`__builtin_expect`): a wait that finds the count at once — every wait of
+// role D, the critical wave — is six instructions of straight-line code, with no branch taken on the way in or out (the loop form enters
+// through an `s_branch` to its header; what a taken branch costs at these sites: profiles/r10_ab_waits.txt).
+template <bool SCALAR = false, bool PEEL = false>
 FBD void duo_wait(DuoSync& sy, int k) {
 #if defined(FB_STAMP) && defined(FB_DUO_WAITPROF)
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #endif
-    const int c = sy.base + k + 1;
+    const int c = (SCALAR ? __builtin_amdgcn_readfirstlane(sy.base) : sy.base) + k + 1;
     asm volatile("" ::: "memory");
     int spins = 0;
+    if constexpr (PEEL) {
+        if (__builtin_expect(__builtin_amdgcn_readfirstlane(*sy.other) < c, 0)) {
+#pragma unroll 1
+            do {
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > (1 << 20)) { sy.failed = 1; break; }
+            } while (__builtin_amdgcn_readfirstlane(*sy.other) < c);
+        }
+    } else {
 #pragma unroll 1
     while (__builtin_amdgcn_readfirstlane(*sy.other) < c) {
         __builtin_amdgcn_s_sleep(1);
@@ -1371,12 +1407,14 @@ FBD void duo_wait(DuoSync& sy, int k) {
         if (++spins > (1 << 20)) { sy.failed = 1; break; }
 #endif
     }
+    }
     asm volatile("" ::: "memory");
 #if defined(FB_STAMP) && defined(FB_DUO_WAITPROF)
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (blockIdx.x == 0 && (threadIdx.x == 0 || threadIdx.x == DUO_B)) {
         const int q = k + (threadIdx.x ? 8 : 0);
         g_stamp_acc[q] += t1 - t0; g_stamp_cnt[q] += 1;
+        g_stamp_acc[4 + q] += spins; g_stamp_cnt[4 + q] += spins != 0;   // the failed passes of this wait; the waits that failed a pass at all
     }
 #endif
 }
@@ -1385,7 +1423,8 @@ FBD void duo_wait(DuoSync& sy, int k) {
 // wave-uniform), instead of the product with `em` and the 64-bit select on `last` in every row of every evaluation:
 //     stages 0-2 (the fall-through):  acc = fma(eb, k, acc)                  x_stage = fma(ee, k, xs)     (A * 1.0 is A for every A: no bit changes)
 //     stage 3:                        A = fma(eb, k, acc), acc = A * 0.0     x_stage = fma(ee, A, xs)     (a product still: the zero keeps A's sign)
-template <int ROLE, bool X = false, int NDL = DUO_ND, bool SUMS_STAY = false, bool STAGE_EMIT = false>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
+// SYNC ("Round 10"): how this role's waits are built (duo_sync_mode()).
+template <int ROLE, bool X = false, int NDL = DUO_ND, bool SUMS_STAY = false, bool STAGE_EMIT = false, int SYNC = 0>   // NDL: how many of role D's stage sums live in LDS (duo_ndl())
 struct DuoEmit {
     static constexpr int role = ROLE;
     static constexpr bool x2 = X;   // the Cessna172Xv2 instance: role D fetches the evaluation's aerodynamic sums behind role P's point R, every publication
@@ -1498,7 +1537,7 @@ struct DuoEmit {
     __device__ __forceinline__ double xget(int k) const { return k < 6 ? xov_l[k * DUO_B + t] : xch_l[(k - 6) * DUO_B + t]; }
     // (Cessna172Xv2: a tapped evaluation hands values over through global memory too — role P's tap rows are released at its point W)
     __device__ __forceinline__ void xpub(int k) const { if (X && tap && ROLE == 1) duo_publish<true>(*sync, k); else duo_publish<false>(*sync, k); }
-    __device__ __forceinline__ void xwait(int k) const { duo_wait(*sync, k); }
+    __device__ __forceinline__ void xwait(int k) const { duo_wait<(SYNC & 1) != 0, (SYNC & 2) != 0>(*sync, k); }
 };
 // every state row of an airborne aircraft belongs to exactly one role, and a role's rows fill its stage-sum slots exactly once
 constexpr bool duo_rows_ok() {
@@ -1713,7 +1752,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
 #pragma unroll 1
         while (true) {
             DUO_MARK(1, 15);  // (arrival at the top of the loop, counted from the previous evaluation's start)
-            duo_wait(sy, DUO_PT_T);   // role D's control and flag words of this evaluation are written, every row of the previous one emitted
+            duo_wait<duo_scalar_sync<KIN, X, PERENV>(), (duo_sync_mode<KIN, X, PERENV>() & 2) != 0>(sy, DUO_PT_T);   // role D's control and flag words of this evaluation are written, every row of the previous one emitted
             DUO_MARK(1, 0);
             if constexpr (X) __builtin_amdgcn_s_setprio(X2_HEAD_PRIO);   // (until its point R: role D reads the evaluation's sums behind it, early in its own evaluation)
             const int c = __builtin_amdgcn_readfirstlane(ctrl_l[pair]);
@@ -1760,7 +1799,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     }
                     DUO_MARK(1, 12);   // (Cessna172Xv2: stage positions and aerodynamic sums formed and stored)
                     asm volatile("" : "+v"(inl.throttle), "+v"(inl.mixture));
-                    const DuoEmit<1, X, DUO_ND, false, duo_stage_emit<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accp_l, acc_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
+                    const DuoEmit<1, X, DUO_ND, false, duo_stage_emit<KIN, X, PERENV>(), duo_sync_mode<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accp_l, acc_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
                                                 tap, i, xn_r};
                     if constexpr (X) {
                         if (tap) {   // what the control laws read of the actuators: the Ranged positions of the state x_{n+1} (InputsX::pos), and the commands this f_ode! saw
@@ -1831,6 +1870,8 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     __builtin_amdgcn_s_setprio(0);
                 }
             }
+            // (scalar for the compiler too, where the instance opts in: the advanced value goes through v_readfirstlane)
+            if constexpr (duo_scalar_sync<KIN, X, PERENV>()) sy.base = __builtin_amdgcn_readfirstlane(sy.base + NPT); else
             sy.base += NPT;
         }
         if constexpr (X) {
@@ -1971,7 +2012,7 @@ __global__ __launch_bounds__(2 * DUO_B) void k_step_duo(KArgs a, int nsteps) {
                     inl.aero_g = ka->duo_pld + il;
                     inl.n = ka->n;
                 }
-                const DuoEmit<2, X, DUO_NDL, duo_sums_stay<KIN, X, PERENV>(), duo_stage_emit<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
+                const DuoEmit<2, X, DUO_NDL, duo_sums_stay<KIN, X, PERENV>(), duo_stage_emit<KIN, X, PERENV>(), duo_sync_mode<KIN, X, PERENV>()> emit = {(lds_cptr)xs_l, sk.xwr_l, (lds_ptr)accd_l, accd_r, (lds_ptr)xch_l, (lds_ptr)xc_l + 15 * B, sk.eb, sk.ee, sk.em, sk.last, t, &sy,
                                             tap_now, i};
                 const SV xv = {sk.xrd_l + t + lds_off};
 #if defined(FB_DUO_ONLY) && FB_DUO_ONLY == 1

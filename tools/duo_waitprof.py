@@ -2,7 +2,10 @@
 """How long each role of the wave-specialised stepper waits for the other (diagnostic build):
     python __graft_entry__.py --diagnostic-variant waitprof -DFB_STAMP -DFB_DUO_WAITPROF
     FLIGHTBATCH_LIB=flight.jl_amd/libflightbatch_waitprof.so python tools/duo_waitprof.py
-Wave 0 (role P) and wave 4 (role D) of workgroup 0: cycles spent in each of the three waits of an evaluation (duo_wait, c172_kernels.hpp)."""
+Wave 0 (role P) and wave 4 (role D) of workgroup 0: cycles spent in each of the three waits of an evaluation (duo_wait, c172_kernels.hpp),
+and the FAILED PASSES of its poll loop: a pass that finds the partner's count is the price of the wait itself, every failed pass issues the
+loop body again (one sleep, one LDS round trip). The instructions a wait issues are (passes that succeed) x (length of that path) + (failed
+passes) x (length of the loop body), with the lengths read from the assembly (docs/design/k_step_duo.md "Round 10")."""
 import ctypes as C, os, sys
 import numpy as np
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,10 +28,13 @@ names_d = ["R: role P has read its state rows (previous evaluation complete)", "
 evals = cnt[0]
 print("launch: %.3f ms per 50 steps of %d aircraft; evaluations profiled: %d" % (ms.value / nl.value, n, evals))
 for role, base, names in (("P (wave 0)", 0, names_p), ("D (wave 4)", 8, names_d)):
-    tot = 0.0
+    tot = ftot = 0.0
     for k in range(3):
         if cnt[base + k]:
             per = acc[base + k] / evals
             tot += per
-            print("%-12s wait %-66s %8.1f cycles per evaluation (x %d)" % (role, names[k], per, cnt[base + k]))
-    print("%-12s total wait %8.1f cycles per evaluation" % (role, tot))
+            fail = acc[base + 4 + k] / evals
+            ftot += fail
+            print("%-12s wait %-66s %8.1f cycles per evaluation (x %d)  %6.3f failed passes per evaluation (%4.1f %% of the waits fail one)"
+                  % (role, names[k], per, cnt[base + k], fail, 100.0 * cnt[base + 4 + k] / cnt[base + k]))
+    print("%-12s total wait %8.1f cycles, %6.3f failed passes per evaluation" % (role, tot, ftot))
