@@ -20,6 +20,8 @@ int32_t fb_lss_connect(fb_handle p, fb_handle c, const int32_t* jz, int32_t nf, 
     if (c && !is_lss(c)) return fail("fb_lss_connect: the compensator is not a LinearizedSS handle (FB_MODEL_LSS: fb_lss_create, fb_lss_from_linearization)");
     if (!p->lss->have_model) return fail("fb_lss_connect: the plant has no model yet (fb_lss_set_model)");
     if (c && !c->lss->have_model) return fail("fb_lss_connect: the compensator has no model yet (fb_lss_set_model)");
+    if (int32_t rc = verb_continuous("fb_lss_connect", p)) return rc;
+    if (c) { if (int32_t rc = verb_continuous("fb_lss_connect", c)) return rc; }
     if (c && c->device != p->device) return fail("fb_lss_connect: the compensator is on device %d, the plant on device %d", c->device, p->device);
     if (c && c->n != p->n) return fail("fb_lss_connect: the compensator has N = %lld systems, the plant N = %lld", (long long)c->n, (long long)p->n);
     const LssState *Lp = p->lss, *Lc = c ? c->lss : nullptr;

@@ -52,6 +52,7 @@ int32_t fb_lss_get_model(fb_handle h, double* A, double* B) {
 int32_t fb_lqr(fb_handle h, const double* Q, const double* R, double* K, double* X, double* resid, int32_t* iters, int32_t* status) {
     if (int32_t rc = verb_handle("fb_lqr", h, FB_LQR_NX_MAX, "design", "FB_LQR_NX_MAX")) return rc;
     if (int32_t rc = verb_model("fb_lqr", h)) return rc;
+    if (int32_t rc = verb_continuous("fb_lqr", h)) return rc;
     const int nx = h->lss->nx, nu = h->lss->nu;
     if (!Q || !R) return fail("fb_lqr: Q and R are required");
     if (!lqr_symmetric(Q, nx)) return fail("fb_lqr: Q is not symmetric");

@@ -11,6 +11,7 @@ struct LssState {
     int xch = 0;                 // the stepper's exchange: 0 LDS panel, 1 cross-lane reads (FLIGHTBATCH_LSS_EXCHANGE, A/B switch for measurements)
     double *ab = nullptr, *xs = nullptr, *u0 = nullptr, *y0 = nullptr, *cd = nullptr;
     bool have_model = false;
+    double Ts = 0;               // > 0: a sampled model made by fb_lss_c2d (fb_c2d.inc): Phi, Gamma and delta in the places of A, B and xdot0
 };
 // blocks of lin_buf that the last lin_run wrote (fb_handle_s::lin_have)
 enum { LIN_HAVE_BASE = 1, LIN_HAVE_X0 = 2, LIN_HAVE_U0 = 4, LIN_HAVE_AB = 8, LIN_HAVE_CD = 16 };
@@ -68,6 +69,10 @@ static int32_t verb_handle(const char* verb, fb_handle h, int nx_max, const char
 }
 static int32_t verb_model(const char* verb, fb_handle h) {
     return h->lss->have_model ? 0 : fail("%s: this LinearizedSS handle has no model yet (fb_lss_set_model)", verb);
+}
+// the design verbs read A and B as a continuous-time model: a sampled handle (fb_lss_c2d) is refused before anything is launched
+static int32_t verb_continuous(const char* verb, fb_handle h) {
+    return h->lss->Ts > 0.0 ? fail("%s: a continuous-time verb on a sampled model (this handle was made by fb_lss_c2d, Ts = %g)", verb, h->lss->Ts) : 0;
 }
 // the model's fields of a verb's argument struct from the handle: [A | B] with its sizes; for a verb on a channel also [C | D], nu and ny
 template <class A> static void verb_args_ab(A& a, fb_handle h) { a.ab = h->lss->ab; a.n = h->n; a.nx = h->lss->nx; a.G = h->lss->G; }
@@ -157,6 +162,7 @@ static int32_t lss_rows(fb_handle h, double* dev, const double* host_in, double*
 }
 static int32_t lss_f_ode(fb_handle h, double* xdot) {
     if (int32_t rc = lss_ready(h)) return rc;
+    if (xdot && h->lss->Ts > 0.0) return fail("fb_f_ode: a sampled model (fb_lss_c2d) has no derivative: pass xdot = NULL to refresh the outputs");
     fbl::LssArgs a = lss_args(h);
     a.xdot = xdot ? h->xdot : nullptr;
     lss_with_group(h->lss, [&](auto G) { hipLaunchKernelGGL(fbl::k_lss_f_ode<G.value>, lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a); });
@@ -164,17 +170,25 @@ static int32_t lss_f_ode(fb_handle h, double* xdot) {
     if (xdot) return lss_rows(h, h->xdot, nullptr, xdot, h->lss->nx);
     return 0;
 }
-// nsteps of k_lss_rk4, steps_per_launch to a launch; u is held over the call, t is advanced here
+// nsteps of k_lss_rk4, or of k_lss_map on a sampled handle (whose step is Ts), steps_per_launch to a launch; u is held over the call, t is
+// advanced here
 static int32_t lss_step(fb_handle h, int64_t nsteps) {
     const LssState* L = h->lss;
+    const bool sampled = L->Ts > 0.0;
+    if (sampled && memcmp(&h->params.dt, &L->Ts, sizeof(double)) != 0)
+        return fail("fb_step: this handle is a sampled model with Ts = %.17g (fb_lss_c2d) and its dt was changed to %.17g: a sampled model steps by its own sample time only", L->Ts, h->params.dt);
     const fbl::LssArgs a = lss_args(h);
     int64_t left = nsteps;
     while (left > 0) {
         const int k = (int)(left < h->steps_per_launch ? left : h->steps_per_launch);
         const int32_t rc = stamped(h, [&] {
             lss_with_group(L, [&](auto G) {
-                if (L->xch == 0) hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 0>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
-                else hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 1>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+                if (!sampled) {
+                    if (L->xch == 0) hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 0>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+                    else hipLaunchKernelGGL((fbl::k_lss_rk4<G.value, 1>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+                }
+                else if (L->xch == 0) hipLaunchKernelGGL((fbz::k_lss_map<G.value, 0>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
+                else hipLaunchKernelGGL((fbz::k_lss_map<G.value, 1>), lss_grid(h), dim3(fbl::LSS_BLOCK), 0, h->stream, a, k);
             });
         });
         if (rc) return rc;
@@ -284,6 +298,7 @@ int32_t fb_lss_set_model(fb_handle h, const double* xdot0, const double* x0, con
                          const double* A, const double* B, const double* C, const double* D) {
     if (!h) return fail("null handle");
     if (!is_lss(h)) return fail("fb_lss_set_model: the handle is not a LinearizedSS handle (fb_lss_create)");
+    if (h->lss && h->lss->Ts > 0.0) return fail("fb_lss_set_model: the handle is a sampled model made by fb_lss_c2d: its model is not replaced (discretise the new model instead)");
     if (!xdot0 || !x0 || !u0 || !y0 || !A || !B || !C || !D) return fail("fb_lss_set_model: every block of the model is required");
     HIPCHK(hipSetDevice(h->device));
     const LssState* L = h->lss;

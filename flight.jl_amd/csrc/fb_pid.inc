@@ -8,6 +8,7 @@
 static int32_t pid_check_plant(const char* verb, fb_handle h, int32_t iu, int32_t iy, const double* w, int32_t nw) {
     if (int32_t rc = verb_handle(verb, h, FB_PID_NX_MAX, "design", "FB_PID_NX_MAX")) return rc;
     if (int32_t rc = verb_model(verb, h)) return rc;
+    if (int32_t rc = verb_continuous(verb, h)) return rc;
     const LssState* L = h->lss;
     if (iu < 0 || iu >= L->nu) return fail("%s: iu = %d is outside [0, %d)", verb, (int)iu, L->nu);
     if (iy < 0 || iy >= L->ny) return fail("%s: iy = %d is outside [0, %d)", verb, (int)iy, L->ny);

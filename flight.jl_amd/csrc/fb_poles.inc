@@ -8,6 +8,7 @@ extern "C" {
 int32_t fb_lss_poles(fb_handle h, double* re, double* im, int32_t* iters, int32_t* status) {
     if (int32_t rc = verb_handle("fb_lss_poles", h, FB_POLES_NX_MAX, "call", "FB_POLES_NX_MAX")) return rc;
     if (int32_t rc = verb_model("fb_lss_poles", h)) return rc;
+    if (int32_t rc = verb_continuous("fb_lss_poles", h)) return rc;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->n, np = (size_t)h->lss->nx * n;
     // one device block: re | im; iters, status apart

@@ -15,6 +15,7 @@ int32_t fb_lss_transform(fb_handle src, const int32_t* rows, const int32_t* xdot
     *out = nullptr;
     if (int32_t rc = verb_handle(verb, src, fbl::LSS_NX_MAX, "transform", "a LinearizedSS handle's")) return rc;
     if (int32_t rc = verb_model(verb, src)) return rc;
+    if (int32_t rc = verb_continuous(verb, src)) return rc;
     const LssState* L = src->lss;
     const int nx = L->nx, nu = L->nu, ny = L->ny;
     if (!ix) nxo = nx;
@@ -60,6 +61,7 @@ int32_t fb_lss_steady(fb_handle h, const int32_t* iz, int32_t nz, const double* 
     static const char* verb = "fb_lss_steady";
     if (int32_t rc = verb_handle(verb, h, FB_SURGERY_N_MAX - 1, "steady-state map", "nx + nu <= FB_SURGERY_N_MAX")) return rc;
     if (int32_t rc = verb_model(verb, h)) return rc;
+    if (int32_t rc = verb_continuous(verb, h)) return rc;
     const LssState* L = h->lss;
     const int nx = L->nx, nu = L->nu, ny = L->ny;
     if (nx + nu > FB_SURGERY_N_MAX) return fail("fb_lss_steady: nx + nu = %d exceeds FB_SURGERY_N_MAX = %d", nx + nu, (int)FB_SURGERY_N_MAX);

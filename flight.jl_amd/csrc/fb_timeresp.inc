@@ -23,6 +23,12 @@ int32_t fb_lss_stepinfo(fb_handle h, const int32_t* iu, const int32_t* iy, int32
         if (iu[j] < 0 || iu[j] >= L->nu) return fail("fb_lss_stepinfo: iu[%d] = %d is outside [0, %d)", j, (int)iu[j], L->nu);
         if (iy[j] < 0 || iy[j] >= L->ny) return fail("fb_lss_stepinfo: iy[%d] = %d is outside [0, %d)", j, (int)iy[j], L->ny);
     }
+    const bool sampled = L->Ts > 0.0;   // (fb_lss_c2d: the samples are the map's, at t_k = k Ts)
+    if (sampled) {
+        if (dt == 0.0 || !std::isfinite(dt)) dt = L->Ts;
+        if (memcmp(&dt, &L->Ts, sizeof(double)) != 0)
+            return fail("fb_lss_stepinfo: dt = %.17g on a sampled model with Ts = %.17g (fb_lss_c2d): pass its Ts, or 0 for it", dt, L->Ts);
+    }
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail("fb_lss_stepinfo: dt = %g must be positive and finite", dt);
     if (!(t_sim >= dt) || !std::isfinite(t_sim)) return fail("fb_lss_stepinfo: t_sim = %g must be finite and at least dt = %g", t_sim, dt);
     const double steps = std::round(t_sim / dt);
@@ -53,7 +59,9 @@ int32_t fb_lss_stepinfo(fb_handle h, const int32_t* iu, const int32_t* iy, int32
     a.y0_in = y0_in ? d_y0 : nullptr; a.yf_in = yf_in ? d_yf : nullptr; a.y = y ? d_y : nullptr; a.info = d_info; a.status = d_st;
     a.m = m; a.nsteps = N; a.stride = stride; a.ns = ns;
     a.dt = dt; a.settling_th = th; a.rise_lo = lo; a.rise_hi = hi;
-    if (int32_t rc = family_launch(h, group_for(a.nx + 1), (int64_t)nc, a, [](auto P) { return fbt::k_timeresp<P.value>; })) return rc;
+    if (!sampled) {
+        if (int32_t rc = family_launch(h, group_for(a.nx + 1), (int64_t)nc, a, [](auto P) { return fbt::k_timeresp<P.value>; })) return rc;
+    } else if (int32_t rc = family_launch(h, group_for(a.nx + 1), (int64_t)nc, a, [](auto P) { return fbz::k_timeresp_map<P.value>; })) return rc;
     if (y) HIPCHK(hipMemcpyAsync(y, d_y, sizeof(double) * n_y, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(info, d_info, sizeof(double) * 9 * nc, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, h->stream));

@@ -138,3 +138,32 @@ __global__ __launch_bounds__(LSS_BLOCK) void k_lss_gather(LssSrc s, LssDst d) {
 }
 
 }  // namespace fbl
+
+// The stepper of a sampled model (fb_lss_c2d; docs/design/linearize.md, "Sampled models on the device"): the handle's copy holds Phi in A's
+// place, Gamma in B's and delta in xdot0's, and a step is the map itself,
+//   x+ = x0 + Phi (x - x0) + Gamma (u - u0) + delta,
+// one exchange where k_lss_rk4 takes four. Groups, exchanges and arguments are k_lss_rk4's; row r of Phi stays in registers with the
+// launch constant delta_r + sum_c Gamma_rc (u_c - u0_c), and the step loop touches no global memory. (Its own namespace: fbl::k_lss_* is
+// the set of the continuous model's instances.)
+namespace fbz {
+
+template <int G, int XCH>
+__global__ __launch_bounds__(fbl::LSS_BLOCK) void k_lss_map(fbl::LssArgs a, int nsteps) {
+    __shared__ __attribute__((aligned(16))) double panel[XCH == 0 ? fbl::LSS_BLOCK : 2];
+    const int r = threadIdx.x % G;
+    const int64_t i = (int64_t)blockIdx.x * (fbl::LSS_BLOCK / G) + threadIdx.x / G;
+    if (i >= a.n) return;   // (whole groups leave together; nothing below is a workgroup barrier)
+    const int64_t S = a.n * G, slot = i * G + r;
+    double prow[G];
+#pragma unroll
+    for (int c = 0; c < G; c++) prow[c] = a.ab[fbg::ab_index(S, slot, c)];
+    const double x0 = a.xs[S + slot], c0 = fbl::lss_const<G>(a, i, slot);
+    const bool live = r < a.nx;
+    double x = live ? a.x[(int64_t)r * a.n + i] : 0.0;
+    const fbg::Exchange<G, XCH> ex(panel);
+#pragma unroll 1
+    for (int k = 0; k < nsteps; k++) x = x0 + ex.dot(prow, x - x0, c0);
+    if (live) a.x[(int64_t)r * a.n + i] = x;
+}
+
+}  // namespace fbz

@@ -9,7 +9,7 @@
 //             iu = trapz|u - 1| / t_N, up = max_k |u_k - 1| (the reference's expression, its "- 1" on the control signal included, :54-60);
 //             Ms = min(1e3, max_j 1 / |1 + P(j w_j) C(j w_j)|) over the caller's grid, P(jw) = c inv(jw I - A) b + d;  cost = sum w m / sum w
 // Differences from the reference: ControlSystems.step picks its own sample time and discretises exactly, here dt is the caller's and the
-// integrator is RK4; hinfnorm2 finds the exact peak and is infinite (-> 1e3) for an unstable loop, here Ms is the grid's peak and an
+// integrator is RK4 (the exact map exists since fb_lss_c2d, c2d_kernels.hpp; these metrics on it are the follow-up); hinfnorm2 finds the exact peak and is infinite (-> 1e3) for an unstable loop, here Ms is the grid's peak and an
 // unstable loop shows as FB_PID_DIVERGED; NLopt's optimisers are not restated (the search is host-side, flightbatch/pidopt.py).
 //
 // k_lss_freqresp: one (system, frequency) pair per group of P lanes of one wave (P = 8, 16 or 32, the smallest >= nx); lane r owns the complex

@@ -24,6 +24,8 @@ from .connect import ConnectResult, connect, integrator_world, pid_world, state_
 from . import surgery  # noqa: F401
 from .surgery import (TransformResult, SteadyResult, transform, subsystem_world, delete_vars_world, steady_state, integrators_world,  # noqa: F401
                       integral_augmentation, lqr_tracker, c172x_design_model)
+from .c2d import C2dResult, c2d  # noqa: F401  (`c2d` is the verb; the status words are K["FB_C2D_NOT_FINITE"], K["FB_C2D_RANGE"])
+from .timeresp import lsim  # noqa: F401
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)

@@ -65,6 +65,14 @@ class LinearWorld(BatchedWorld):
         self.t = 0.0
         self._Δt_root = 1.0
         self._n = 0
+        self.squarings = None    # [N] on a world made by c2d: the squarings of each system's discretisation
+
+    @property
+    def Ts(self) -> float:
+        """the sample time of a sampled world (flightbatch.c2d); 0.0 on a continuous one"""
+        ts = C.c_double(-1.0)
+        check(lib.fb_lss_sample_time(self._h, C.byref(ts)))
+        return ts.value
 
     # -- mdl.x / mdl.u / mdl.y --
     def set_state(self, x, s=None):   # an INITIAL condition: restarts the clock and the step count (fb_set_state)
@@ -94,7 +102,8 @@ class LinearWorld(BatchedWorld):
         return y
 
     def model(self):
-        """(A [n, nx, nx], B [n, nx, nu]): the handle's own copy of the model, the matrices the device steps and designs on (read-only)"""
+        """(A [n, nx, nx], B [n, nx, nu]): the handle's own copy of the model, the matrices the device steps and designs on (read-only);
+        (Phi, Gamma) on a sampled world"""
         A, B = np.empty(self.nx * self.nx * self.n), np.empty(self.nx * self.nu * self.n)
         check(lib.fb_lss_get_model(self._h, _pd(A), _pd(B)))
         return unpack_matrix(A, self.nx, self.nx), unpack_matrix(B, self.nx, self.nu)
@@ -118,7 +127,8 @@ class LinearWorld(BatchedWorld):
         return xdot
 
     def step(self, nsteps: int = 1, dt: float | None = None, steps_per_launch: int | None = None) -> None:
-        """nsteps of RK4 with u held (asynchronous); dt and the steps fused per launch stay as last set"""
+        """nsteps of RK4 with u held (asynchronous), or of the map on a sampled world (whose dt is its Ts); dt and the steps fused per
+        launch stay as last set"""
         if dt is not None:
             self.set_params(dt=float(dt))
         if steps_per_launch is not None:

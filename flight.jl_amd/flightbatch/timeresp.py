@@ -7,7 +7,10 @@ csrc/timeresp_kernels.hpp; docs/design/linearize.md, "Step responses on the devi
 
 A channel is a pair (iu, iy) of indices into the world's inputs and outputs, or a pair of labels where the world carries them. The response is
 that of the deviation model from rest: xdot0, x0, u0 and y0 play no part. Not the reference's: ControlSystems.step picks its own sample time
-and discretises exactly; here dt is the caller's (default_dt when None) and the integrator is the classical RK4 of the other steppers."""
+and discretises exactly; here dt is the caller's (default_dt when None) and the integrator is the classical RK4 of the other steppers
+(method="rk4", the default) or, with method="zoh", the exact zero-order-hold map of flightbatch.c2d at that dt, whose samples are exact.
+
+    lsim(sys, u, t)                   FA demos/c172_demos.jl:135, 186            timeresp.lsim(world, u, t)    (zero-order hold, existing verbs only)"""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -66,6 +69,7 @@ class StepResult:
     t: np.ndarray        # [ns]        sample times: s stride dt, the last one N dt
     y: np.ndarray        # [N, m, ns]  the response of channel j of system i
     status: np.ndarray   # [N, m]      0, or FB_STEPINFO_DIVERGED / FB_STEPINFO_FLAT
+    c2d_status: np.ndarray | None = None   # [N] method="zoh" on a continuous world: the discretisation's status words (FB_C2D_*), else None
 
 
 @dataclass
@@ -81,10 +85,11 @@ class StepInfo:
     risetime: np.ndarray
     status: np.ndarray        # [N, m] 0, FB_STEPINFO_DIVERGED (every field NaN) or FB_STEPINFO_FLAT (the ratios and times NaN)
     dt: float
+    c2d_status: np.ndarray | None = None   # [N] method="zoh" on a continuous world: the discretisation's status words (FB_C2D_*), else None
 
     @property
     def ok(self) -> np.ndarray:
-        return self.status == 0
+        return (self.status == 0) if self.c2d_status is None else (self.status == 0) & (self.c2d_status == 0)[:, None]
 
     def show(self, i: int = 0, j: int = 0) -> str:
         """the reference's nine lines for channel j of system i, in its print format"""
@@ -97,7 +102,22 @@ class StepInfo:
         return "\n".join("%-19s%s" % r for r in rows)
 
 
-def _call(world, channels, t_sim, dt, opts, y0, yf, stride, want_y):
+def _call(world, channels, t_sim, dt, opts, y0, yf, stride, want_y, method="rk4"):
+    """(dt, nsteps, y, info, status, c2d_status) of one fb_lss_stepinfo call; method="zoh" on a continuous world discretises it at dt first
+    (a temporary sampled world, destroyed afterwards); a sampled world runs its own map at its own Ts"""
+    if method not in ("rk4", "zoh"):
+        raise ValueError('timeresp: method is "rk4" or "zoh"')
+    Ts = world.Ts if isinstance(world, LinearWorld) else 0.0      # (any other world: the library refuses it by name below)
+    if Ts > 0.0:
+        dt = Ts if dt is None else float(dt)
+    elif method == "zoh":
+        from .c2d import c2d
+        dt = default_dt(world) if dt is None else float(dt)
+        res = c2d(world, dt)
+        try:
+            return _call(res.world, channels, t_sim, dt, opts, y0, yf, stride, want_y)[:5] + (res.status,)
+        finally:
+            res.world.close()
     iu, iy = _channels(world, channels)
     m, n = len(iu), world.n
     dt = default_dt(world) if dt is None else float(dt)
@@ -110,21 +130,89 @@ def _call(world, channels, t_sim, dt, opts, y0, yf, stride, want_y):
     check(lib.fb_lss_stepinfo(world._h, _pi(iu), _pi(iy), m, float(t_sim), dt, None if o is None else _pd(o),
                               None if y0p is None else _pd(y0p), None if yfp is None else _pd(yfp), int(stride),
                               None if y is None else _pd(y), _pd(info), _pi(status)))
-    return dt, nsteps, y, info, status
+    return dt, nsteps, y, info, status, None
 
 
-def step(world: LinearWorld, channels, t_sim: float, dt: float | None = None, stride: int = 1) -> StepResult:
-    """the unit step response of every channel of every system of `world`, every `stride`-th sample and the last one"""
-    dt, nsteps, y, _, status = _call(world, channels, t_sim, dt, None, None, None, stride, True)
+def step(world: LinearWorld, channels, t_sim: float, dt: float | None = None, stride: int = 1, method: str = "rk4") -> StepResult:
+    """the unit step response of every channel of every system of `world`, every `stride`-th sample and the last one. method: "rk4", or
+    "zoh" for the exact samples of the zero-order-hold map (c2d at dt); a sampled world is sampled at its own Ts either way."""
+    dt, nsteps, y, _, status, c2d_status = _call(world, channels, t_sim, dt, None, None, None, stride, True, method)
     ns = y.shape[0]
     t = np.arange(ns, dtype=np.float64) * (stride * dt)
     t[-1] = nsteps * dt
-    return StepResult(t=t, y=np.ascontiguousarray(y.transpose(2, 1, 0)), status=status.T.copy())
+    return StepResult(t=t, y=np.ascontiguousarray(y.transpose(2, 1, 0)), status=status.T.copy(), c2d_status=c2d_status)
 
 
 def stepinfo(world: LinearWorld, channels, t_sim: float, dt: float | None = None, y0=None, yf=None, settling_th: float = 0.02,
-             risetime_th=(0.1, 0.9)) -> StepInfo:
+             risetime_th=(0.1, 0.9), method: str = "rk4") -> StepInfo:
     """stepinfo(step(P[:y, :u], t_sim)) of every channel of every system. y0, yf: None, a scalar or [N, m]; NaN entries mean the first / last
-    sample."""
-    dt, _, _, info, status = _call(world, channels, t_sim, dt, (settling_th, risetime_th[0], risetime_th[1]), y0, yf, 1, False)
-    return StepInfo(*[info[k].T.copy() for k in range(9)], status=status.T.copy(), dt=dt)
+    sample. method: as step's."""
+    dt, _, _, info, status, c2d_status = _call(world, channels, t_sim, dt, (settling_th, risetime_th[0], risetime_th[1]), y0, yf, 1, False, method)
+    return StepInfo(*[info[k].T.copy() for k in range(9)], status=status.T.copy(), dt=dt, c2d_status=c2d_status)
+
+
+def lsim(world: LinearWorld, u, t, x0=None):
+    """(y [nt, ny, N], x [nt, nx, N]) of every system of `world` under the input u held over each interval of the uniform time vector t
+    (zero-order hold, exact at the samples): x_{k+1} = x0 + Phi (x_k - x0) + Gamma (u_k - u0) + delta and y_k = y0 + C (x_k - x0) +
+    D (u_k - u0) with the u of sample k. u: [nt, nu] for the batch or [nt, nu, N] per system ([nt] where nu == 1), the inputs themselves
+    (not deviations from u0). x0: the initial state [nx] or [nx, N]; None: the world's current state (a world fresh from linear_world or
+    c2d sits at its linearisation point). A continuous world is discretised at t[1] - t[0] into a temporary world, which is destroyed
+    afterwards, and is itself left untouched; a sampled world must have that Ts, and is left at the last sample with its log off.
+    Existing verbs only: runs of equal consecutive inputs advance in one step() with the device log, and the sample at a change of input is
+    recorded after the new input is set."""
+    if not isinstance(world, LinearWorld):
+        raise FlightBatchError("lsim: the world is not a LinearizedSS handle (FB_MODEL_LSS): give it a LinearWorld")
+    t = np.asarray(t, dtype=np.float64)
+    nt = t.size
+    if t.ndim != 1 or nt < 2:
+        raise ValueError("lsim: t is a vector of at least two instants")
+    dt = float(t[1] - t[0])
+    if not (dt > 0.0) or not np.allclose(np.diff(t), dt, rtol=1e-9, atol=0.0):
+        raise ValueError("lsim: t must be uniform and increasing")
+    n, nx, nu, ny = world.n, world.nx, world.nu, world.ny
+    u = np.asarray(u, dtype=np.float64)
+    if u.ndim == 1 and nu == 1:
+        u = u[:, None]
+    if u.ndim == 2:
+        u = np.broadcast_to(u[:, :, None], u.shape + (n,))
+    if u.shape != (nt, nu, n):
+        raise ValueError(f"lsim: u is [nt, nu] or [nt, nu, N] = [{nt}, {nu}, {n}], got {list(u.shape)}")
+    start = world.x if x0 is None else np.broadcast_to(np.asarray(x0, dtype=np.float64).reshape(nx, -1), (nx, n))
+    Ts = world.Ts
+    own = None
+    if Ts > 0.0:
+        if abs(Ts - dt) > 1e-9 * Ts:
+            raise FlightBatchError(f"lsim: the world is sampled at Ts = {Ts!r}, the time vector steps by {dt!r}")
+        w = world
+    else:
+        from .c2d import c2d
+        own = c2d(world, dt)
+        w = own.world
+        if not own.ok.all():
+            bad = np.flatnonzero(~own.ok)
+            w.close()
+            raise FlightBatchError(f"lsim: c2d flagged systems {bad.tolist()} (status {own.status[bad].tolist()})")
+    try:
+        change = np.flatnonzero((u[1:] != u[:-1]).any(axis=(1, 2))) + 1          # the samples that begin a run
+        starts = np.concatenate([[0], change])
+        w.set_state(np.ascontiguousarray(start))
+        w.log_configure(1, nt + len(starts), y=range(ny), x=range(nx))
+        at = np.empty(nt, dtype=np.int64)      # where sample k lies in the log: its last record
+        pos = 0
+        for j, k in enumerate(starts):
+            end = int(starts[j + 1]) if j + 1 < len(starts) else nt - 1          # the run's input takes the state to sample `end`
+            w.u = np.ascontiguousarray(u[k])
+            check(lib.fb_log_record(w._h))                                     # sample k with the new input (f_ode, then the rows)
+            at[k] = pos
+            steps = end - int(k)
+            if steps > 0:
+                w.step(steps)
+                at[k + 1:end + 1] = pos + 1 + np.arange(steps)
+            pos += 1 + steps
+        _, data = w.log_read()
+        w.log_configure(0, 0)
+    finally:
+        if own is not None:
+            w.close()
+    data = data[at]
+    return np.ascontiguousarray(data[:, :ny]), np.ascontiguousarray(data[:, ny:])

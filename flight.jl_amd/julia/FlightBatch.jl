@@ -397,6 +397,22 @@ function steady_state(w::LinearWorld, z; k::Union{Array{Float64}, Nothing} = not
                 w.handle, iz, nz, k === nothing ? C_NULL : k, k !== nothing && ndims(k) == 3 ? 1 : 0, x, u, k === nothing ? C_NULL : k_fwd, rpiv, status))
     return (; x, u, k_fwd, status, rpiv)
 end
+"`c2d(sys, Ts)` on the device: the zero-order-hold sampled model of every system of a continuous `LinearWorld` (Phi = e^(A Ts) in A's place,
+Gamma in B's, delta in xdot0's; x+ = x0 + Phi (x - x0) + Gamma (u - u0) + delta), a new `LinearWorld` whose step is the map and whose dt is
+Ts. Returns the world, status (0, FB_C2D_NOT_FINITE = 1 or FB_C2D_RANGE = 2: that system's Phi, Gamma and delta are NaN) and the squarings
+of each system's scaling and squaring. The continuous-time design verbs refuse a sampled world; `sample_time(w)` is its Ts (0 for a
+continuous one)."
+function c2d(w::LinearWorld, ts::Real)
+    status = Vector{Int32}(undef, w.n); squarings = Vector{Int32}(undef, w.n)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_c2d, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Int32}, Ptr{Int32}, Ptr{Ptr{Cvoid}}), w.handle, Float64(ts), squarings, status, h))
+    return (; world = LinearWorld(h[]), status, squarings)
+end
+function sample_time(w::LinearWorld)
+    ts = Ref{Cdouble}(0.0)
+    check(ccall((:fb_lss_sample_time, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, ts))
+    return ts[]
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

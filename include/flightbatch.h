@@ -384,8 +384,8 @@ int32_t fb_lss_freqresp(fb_handle lss, int32_t iu, int32_t iy, const double* w, 
  * the reference's expression). cost [m x N] = sum weights m / sum weights (:66-70); weights [5] >= 0 with a positive sum, NULL = ones.
  * status [m x N]: 0; FB_PID_DIVERGED: a sample was not finite or beyond 1e12 (ie, ef, iu, up and cost are +Inf, Ms is the grid's);
  * FB_PID_SINGULAR: a zero or non-finite pivot at some frequency, or 1 + d (k_p + k_d / tau_f) = 0 (the metrics are NaN, cost is +Inf).
- * The call returns 0 in both cases. Not the reference's: its step() picks the sample time and discretises exactly, and its hinfnorm2 finds
- * the exact peak and is infinite for an unstable loop. */
+ * The call returns 0 in both cases. Not the reference's: its step() picks the sample time and discretises exactly (here: fb_lss_c2d, which
+ * this verb does not use yet), and its hinfnorm2 finds the exact peak and is infinite for an unstable loop. */
 enum { FB_PID_DIVERGED = 1, FB_PID_SINGULAR = 2, FB_PID_NX_MAX = 28 };
 int32_t fb_pid_metrics(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double t_sim, double dt, const double* weights,
                        const double* pid, int32_t m, double* metrics, double* cost, int32_t* status);
@@ -423,7 +423,8 @@ int32_t fb_lss_poles(fb_handle lss, double* re, double* im, int32_t* iters, int3
  * status [m x N]: 0; FB_STEPINFO_DIVERGED: a sample was not finite or beyond 1e12 (every info row is NaN); FB_STEPINFO_FLAT: stepsize is 0
  * or not finite (y0, yf, stepsize, peak and peaktime as defined with dir = +1; the four ratios and times are NaN). The call returns 0 in both
  * cases. Reads the handle's copy of the model, runs on its stream and changes nothing on the handle. Not the reference's: its step() picks
- * the sample time and discretises exactly. */
+ * the sample time and discretises exactly; the exact samples at the caller's dt are those of the same call on the handle fb_lss_c2d makes
+ * (below), which samples the map instead of integrating. */
 enum { FB_STEPINFO_DIVERGED = 1, FB_STEPINFO_FLAT = 2, FB_STEPINFO_NX_MAX = 31 };
 int32_t fb_lss_stepinfo_samples(int32_t nsteps, int32_t stride);   /* -1 unless nsteps >= 1 and stride >= 1 */
 int32_t fb_lss_stepinfo(fb_handle lss, const int32_t* iu, const int32_t* iy, int32_t m, double t_sim, double dt, const double* opts,
@@ -483,6 +484,29 @@ int32_t fb_lss_transform(fb_handle lss, const int32_t* rows, const int32_t* xdot
                          const int32_t* iy, int32_t nyo, int32_t* status, double* rpiv, fb_handle* out);
 int32_t fb_lss_steady(fb_handle lss, const int32_t* iz, int32_t nz, const double* K, int32_t k_per_system, double* X, double* U, double* K_fwd,
                       double* rpiv, int32_t* status);
+
+/* ---- sampled models: zero-order-hold discretisation on the device (the exact samples of ControlSystems' step and lsim, FA design/pidopt.jl,
+ * demos/c172_demos.jl:135, 186; docs/design/linearize.md, "Sampled models on the device") ---------------------------------------------------
+ * fb_lss_c2d: for every system of a continuous FB_MODEL_LSS handle (1 <= nx <= 32, every nu and ny the handle admits), with
+ *     Psi = int_0^Ts e^(A tau) dtau:   Phi = e^(A Ts) = I + A Psi,  Gamma = Psi B,  delta = Psi xdot0
+ * a new FB_MODEL_LSS handle of the same N, nx, nu, ny whose copy of the model holds Phi in A's place, Gamma in B's and delta in xdot0's; C, D,
+ * x0, u0 and y0 are copied bit for bit. The affine offset is carried exactly: x+ = x0 + Phi (x - x0) + Gamma (u - u0) + delta. The new handle
+ * is marked sampled with sample time Ts: its dt is Ts, x = x0, u = u0, t = 0; on the source's device, with its stream rule
+ * (fb_lss_from_linearization). The source is only read. By scaling and squaring of the pair (Phi, Psi [B | xdot0]) with s = the smallest
+ * integer >= 0 with |A|_inf Ts / 2^s <= 1/2; A is never inverted (a singular A, an integrator in series, is an ordinary input).
+ * squarings [N] and status [N] may be NULL. status: 0; FB_C2D_NOT_FINITE: a non-finite entry of A, B or xdot0, or a non-finite result (an
+ * overflowing e^(A Ts)); FB_C2D_RANGE: s would exceed FB_C2D_SQUARINGS_MAX. Such a system gets Phi, Gamma and delta all NaN; the call still
+ * returns 0 and no other system changes in any bit. squarings: s (0 where there is a status). Refused, with nothing launched and no handle
+ * created: a NULL or non-LSS handle, a handle without a model, a handle that is itself sampled, Ts not finite or <= 0, a NULL out.
+ * fb_lss_sample_time: Ts of a sampled handle, 0 for a continuous LinearizedSS handle.
+ * A sampled handle under the other verbs: fb_step applies the map (one step = Ts on the clock; refused once fb_set_params has made dt differ
+ * from Ts in any bit); fb_f_ode(NULL) refreshes y, fb_f_ode(xdot) is refused (no derivative); fb_lss_get_model returns Phi and Gamma;
+ * fb_lss_get_cd is unchanged; fb_lss_stepinfo samples the map at t_k = k Ts (dt must be Ts bit for bit; 0 or a non-finite dt means Ts);
+ * fb_lss_set_model, fb_lss_c2d, fb_lqr, fb_pid_metrics, fb_lss_freqresp, fb_lss_poles, fb_lss_connect (either argument),
+ * fb_lss_transform and fb_lss_steady are refused ("a continuous-time verb on a sampled model"). */
+enum { FB_C2D_NOT_FINITE = 1, FB_C2D_RANGE = 2, FB_C2D_SQUARINGS_MAX = 30 };
+int32_t fb_lss_c2d(fb_handle lss, double Ts, int32_t* squarings /* [N] or NULL */, int32_t* status /* [N] or NULL */, fb_handle* out);
+int32_t fb_lss_sample_time(fb_handle h, double* Ts);   /* 0 for a continuous LinearizedSS handle */
 
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
