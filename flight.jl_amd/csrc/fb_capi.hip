@@ -18,6 +18,7 @@
 #include "lss_kernels.hpp"
 #include "lqr_kernels.hpp"
 #include "pid_kernels.hpp"
+#include "margins_kernels.hpp"
 #include "poles_kernels.hpp"
 #include "timeresp_kernels.hpp"
 #include "connect_kernels.hpp"
@@ -223,6 +224,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 #include "fb_lss.inc"
 #include "fb_lqr.inc"
 #include "fb_pid.inc"
+#include "fb_margins.inc"
 #include "fb_poles.inc"
 #include "fb_timeresp.inc"
 #include "fb_connect.inc"

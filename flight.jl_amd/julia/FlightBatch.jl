@@ -413,6 +413,25 @@ function sample_time(w::LinearWorld)
     check(ccall((:fb_lss_sample_time, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, ts))
     return ts[]
 end
+"`marginplot`'s numbers on the device: gain and phase margins of L = gain (c inv(jωI - A) b + d) of channel (iu, iy) (1-based) of every system
+of a continuous `LinearWorld` under negative unity feedback, from the brackets of the grid `freqs` (rad/s, positive, strictly increasing),
+each refined by bisection. `gain`: `nothing` (ones), a number for the batch or a vector of N. Returns gm (a factor; +Inf without a phase
+crossing), wpc, pm (degrees; +Inf without a gain crossing), wgc, ms and wms (the peak of 1 / |1 + L| over the grid and its frequency), npc,
+ngc, status (0 or FB_MARGINS_NOT_FINITE = 1, FB_MARGINS_SINGULAR = 2: that system's numbers are NaN; FB_MARGINS_TRUNCATED = 4: more than
+8 crossings of a kind), sel (N x 10, the rows of `fb_lss_margins`) and, with `all = true`, every kept crossing as an N x 8 x 6 array
+(ω*, Re L*, Im L* of the phase crossings, then of the gain crossings). Margins say nothing about closed-loop stability: `poles` of the
+closed loop does."
+function margins(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64}; gain = nothing, all::Bool = false)
+    g = gain === nothing ? nothing : (gain isa Real ? fill(Float64(gain), w.n) : Vector{Float64}(gain))
+    g === nothing || length(g) == w.n || throw(DimensionMismatch("margins: gain has $(length(g)) entries for $(w.n) systems"))
+    sel = Matrix{Float64}(undef, w.n, 10); counts = Matrix{Int32}(undef, w.n, 2); status = Vector{Int32}(undef, w.n)
+    every = all ? Array{Float64}(undef, w.n, 8, 6) : nothing
+    check(ccall((:fb_lss_margins, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), g === nothing ? C_NULL : g, sel, counts, every === nothing ? C_NULL : every, status))
+    return (; gm = sel[:, 1], wpc = sel[:, 2], pm = sel[:, 3], wgc = sel[:, 4], ms = 1.0 ./ sel[:, 9], wms = sel[:, 10],
+            npc = counts[:, 1], ngc = counts[:, 2], status, sel, all = every)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

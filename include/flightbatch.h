@@ -508,6 +508,43 @@ enum { FB_C2D_NOT_FINITE = 1, FB_C2D_RANGE = 2, FB_C2D_SQUARINGS_MAX = 30 };
 int32_t fb_lss_c2d(fb_handle lss, double Ts, int32_t* squarings /* [N] or NULL */, int32_t* status /* [N] or NULL */, fb_handle* out);
 int32_t fb_lss_sample_time(fb_handle h, double* Ts);   /* 0 for a continuous LinearizedSS handle */
 
+/* ---- gain and phase margins of a batch of loops (FA design/robot2d/robot2d_design.ipynb: `marginplot(P_v[:η, :v_ref])` and
+ * `marginplot(series(C_η2v, P_v2η))`; docs/design/linearize.md, "Margins on the device") -----------------------------------------------------
+ * The loop of system i is L_i(jw) = gain_i (c inv(jw I - A) b + d) of channel (iu, iy) of a continuous FB_MODEL_LSS handle with a model and
+ * 1 <= nx <= FB_MARGINS_NX_MAX, in deviation coordinates, under negative unity feedback (the closed loop is 1 + L). gain [N] or NULL (ones).
+ * w [nw]: 2 <= nw <= 1024 frequencies in rad/s, positive, finite and strictly increasing. With L_k = L(j w_k), interval k brackets
+ *   a phase crossing when (Im L_k < 0) != (Im L_k+1 < 0), unless Re L >= 0 at both ends (a crossing of the positive real axis);
+ *   a gain crossing when (|L_k|^2 < 1) != (|L_k+1|^2 < 1).
+ * Every bracket is refined by geometric bisection on its own predicate: mid = sqrt(lo hi); stop when mid is not strictly inside (lo, hi) or
+ * after 60 halvings; lo = mid when the predicate at mid equals the one at lo, else hi = mid. The crossing is w* = the final lo, L* = L(j w*).
+ * A refined phase bracket counts when Re L* < 0 (gm = -1 / Re L*), a refined gain bracket always (pm = atan2(-Im L*, -Re L*) in degrees, in
+ * (-180, 180]). At most FB_MARGINS_KMAX crossings of a kind are kept, in ascending frequency; one more sets FB_MARGINS_TRUNCATED and the
+ * count stays at FB_MARGINS_KMAX. Selected: the kept phase crossing with the smallest max(g, 1 / g), g = -Re L* (the gain margin closest to
+ * 1 in either direction), and the kept gain crossing with the largest -Re L* / |L*| (the smallest |pm|); ties go to the lower frequency.
+ * The device selects by comparing products; gm, pm and the square root of smin are computed by the host side of this call.
+ * sel [10 x N], row order gm, wpc, pm, wgc, Re L* and Im L* at the phase crossing, Re L* and Im L* at the gain crossing, smin = the minimum
+ * over the grid of |1 + L_k| (the grid's value, as fb_pid_metrics' Ms is: Ms = 1 / smin), wsmin = the grid frequency of smin (the lower one
+ * at a tie). Without a phase crossing gm = +Inf and wpc, Re, Im = NaN; without a gain crossing pm = +Inf and wgc, Re, Im = NaN.
+ * counts [2 x N]: the kept phase crossings, the kept gain crossings. all (may be NULL) [6 x FB_MARGINS_KMAX x N]: rows w*, Re L*, Im L* of
+ * the phase crossings, then of the gain crossings, slot s of row q of system i at all[(q FB_MARGINS_KMAX + s) N + i], NaN past the count.
+ * Every array has the system index fastest: element (k, i) at [k N + i].
+ * status [N]: 0; FB_MARGINS_NOT_FINITE: a non-finite entry of A, b, c, d or the gain; FB_MARGINS_SINGULAR: a zero or non-finite pivot, or a
+ * non-finite L, at a grid point or a refinement point (a pole on the imaginary axis hit exactly). Such a system gets NaN in sel and all and
+ * zero counts; the call still returns 0 and no other system changes in any bit. FB_MARGINS_TRUNCATED voids nothing.
+ * Reads the handle's copy of the model, runs on its stream (fb_lss_freqresp's kernel on the grid, in slices of whole frequencies of at most
+ * 2^25 one-wave workgroups each, one slice unless N nw passes 2^31 / P pairs, P = 8, 16 or 32 the smallest >= nx; then the margins' kernel)
+ * and changes nothing on the handle. For the length of the call the grid response, 2 nw N doubles, is held on the device.
+ * Refused, with nothing launched: a NULL or non-LSS handle, a handle without a model, a sampled handle ("a continuous-time verb on a sampled
+ * model"), iu or iy out of range, a NULL w, sel, counts or status, nw outside [2, 1024], a grid entry that is not positive and finite, a grid
+ * that does not strictly increase, N nw above 2^31 - 1.
+ * Limits: a bracket around a lightly damped or undamped pole pair refines onto the pole (a margin near zero, or FB_MARGINS_SINGULAR);
+ * crossings the grid does not bracket are not found; margins say nothing about closed-loop stability (fb_lss_poles of the closed loop does). */
+enum { FB_MARGINS_NOT_FINITE = 1, FB_MARGINS_SINGULAR = 2, FB_MARGINS_TRUNCATED = 4,
+       FB_MARGINS_KMAX = 8, FB_MARGINS_NX_MAX = 32 };
+int32_t fb_lss_margins(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, const double* gain /* [N] or NULL */,
+                       double* sel /* [10 x N] */, int32_t* counts /* [2 x N] */, double* all /* [6 x KMAX x N] or NULL */,
+                       int32_t* status /* [N] */);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
