@@ -6,7 +6,8 @@
 // workgroups per CU (two waves per SIMD), so one wave's LDS / memory waits are covered by the other's arithmetic, and
 // every 64-bit move, select and transcendental expansion of the fp64 path shrinks.
 //
-// Precision design (errors measured against the fp64 oracle in tests/test_gpu_f32.py):
+// Precision design (errors measured against the fp64 oracle in tests/test_gpu_f32.py over 1000 smooth steps and, through events, hand-overs,
+// throws and batch edges, in tests/test_gpu_f32_events.py and tests/test_gpu_f32_edges.py; docs/design/k_step_air.md has the numbers):
 //   * the state lives in HBM in fp64 for every instance, so handles, ABI and the other kernels are unchanged;
 //   * the position states q_ew[4], h_e are INTEGRATED in fp64 (their per-step increments are ~1e-8 of their magnitude,
 //     below fp32 resolution: in fp32 the aircraft would not move over the Earth); the RHS reads them rounded to fp32;
@@ -66,14 +67,22 @@ struct F32Emit {
             for (int e = 0; e < NE; e++) {
                 const int j = j0 + e, r = SV::row(j), idx = r * B + t;
                 aset(r, 0.0f);
+#ifndef FB_F32_WIDE_EE_DEFECT   // (-DFB_F32_WIDE_EE_DEFECT rebuilds a defect the tests must see: the fp32 weight dt/6 on the fp64-integrated rows; profiles/f32_defect_builds.txt)
                 if (wide(j)) { const double v = xsd[e] + eed * ((double)ac[e] + (double)eb * (double)k[e]); xc_l[idx] = (float)v; xp_l[(j - XP0) * B + t] = v; }
+#else
+                if (wide(j)) { const double v = xsd[e] + (double)ee * ((double)ac[e] + (double)eb * (double)k[e]); xc_l[idx] = (float)v; xp_l[(j - XP0) * B + t] = v; }
+#endif
                 else { const float v = __builtin_fmaf(ee, __builtin_fmaf(eb, k[e], ac[e]), xsf[e]); xc_l[idx] = v; xs_l[xsrow(r) * B + t] = v; }
             }
         } else {
 #pragma unroll
             for (int e = 0; e < NE; e++) {
                 const int j = j0 + e, r = SV::row(j), idx = r * B + t;
+#ifndef FB_F32_WIDE_EB_DEFECT   // (-DFB_F32_WIDE_EB_DEFECT: k2 and k3 of the fp64-integrated rows summed with weight 1)
                 if (wide(j)) { aset(r, (float)((double)ac[e] + (double)eb * (double)k[e])); xc_l[idx] = (float)(xsd[e] + eed * (double)k[e]); }
+#else
+                if (wide(j)) { aset(r, (float)((double)ac[e] + (double)k[e])); xc_l[idx] = (float)(xsd[e] + eed * (double)k[e]); }
+#endif
                 else { aset(r, __builtin_fmaf(eb, k[e], ac[e])); xc_l[idx] = __builtin_fmaf(ee, k[e], xsf[e]); }
             }
         }
@@ -208,7 +217,9 @@ __global__ __launch_bounds__(fbd::STEP_BLOCK, 2) FB_NO_PK32 void k_step_f32(fbd:
 #pragma unroll
                     for (int r = 0; r < NRF; r++) {
                         xc_l[r * B + t] = (r >= RP0 && r < RP0 + XPN) ? (float)xp_l[(r - RP0) * B + t] : xs_l[xsrow(r) * B + t];
+#ifndef FB_F32_REDO_ACC_DEFECT   // (-DFB_F32_REDO_ACC_DEFECT rebuilds a defect the tests must see: the discarded k1 left in the stage sums)
                         if (r < F32_NAL) acc_l[r * B + t] = 0.0f; else acc_r[r - F32_NAL] = 0.0f;   // (it held the discarded k1)
+#endif
                     }
                 }
                 run = mod; redoing = true;

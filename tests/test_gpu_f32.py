@@ -74,6 +74,12 @@ def test_f32_hands_ground_contact_to_the_fp64_kernel(fb, oracle):
     wow_o = (yo[fb.K["FB_Y_LDG"] + 1] + yo[fb.K["FB_Y_LDG"] + 12] + yo[fb.K["FB_Y_LDG"] + 23]) > 0
     print("on wheels: gpu %d, oracle %d; terminated gpu %d oracle %d" % (wow[ok].sum(), wow_o[ok].sum(), (w.status[ok] != 0).sum(), (sto[ok] != 0).sum()))
     assert wow[ok].sum() > 5 and abs(int(wow[ok].sum()) - int(wow_o[ok].sum())) <= max(3, wow_o[ok].sum() // 10)
+    # the status words are the oracle's, on every lane whose word the oracle settles more than one step from the end of the run: still
+    # flying two steps behind it, or terminated two steps ahead of it (a word can only change where a simulation ends)
+    _, _, sto2, tso2, _ = oracle.step_term(x0, u0, ui0, s0, env, 0.01, 602)
+    settled = ok & ((sto2 == 0) | ((tso2 >= 0) & (tso2 <= 598)))
+    print("status words held to the oracle's on %d of %d lanes (%d of them terminated)" % (settled.sum(), ok.sum(), (sto[settled] != 0).sum()))
+    assert settled.sum() > 0.9 * ok.sum() and np.array_equal(w.status[settled], sto[settled])
     live = ok & (sto == 0) & (w.status == 0)
     assert live.sum() > 0.9 * ok.sum()
     h_err = np.abs(w.x[20] - xo[20])[live]
