@@ -24,6 +24,7 @@
 #include "connect_kernels.hpp"
 #include "surgery_kernels.hpp"
 #include "c2d_kernels.hpp"
+#include "dlqr_kernels.hpp"
 
 using namespace fbd;
 
@@ -230,6 +231,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 #include "fb_connect.inc"
 #include "fb_surgery.inc"
 #include "fb_c2d.inc"
+#include "fb_dlqr.inc"
 struct ncclUniqueIdBlob { char internal[128]; };   // ncclUniqueId (rccl.h:40-43), passed by value
 
 // The scratch rows of the stepping kernels (ctl_bak, duo_pld, duo_tap) are zeroed when a handle is created: hipMalloc hands out zero pages in

@@ -16,7 +16,7 @@ from . import scenario  # noqa: F401
 from .fleet import MixedFleet  # noqa: F401
 from .linearization import LinearizedSS, linearize, linearize_state, subsystem, delete_vars  # noqa: F401
 from .lss import LinearWorld, linear_world  # noqa: F401
-from .lqr import LqrResult, lqr, closed_loop, design_model  # noqa: F401
+from .lqr import LqrResult, lqr, closed_loop, design_model, DlqrResult, dlqr  # noqa: F401
 from .poles import PolesResult, poles, dampreport  # noqa: F401
 from . import timeresp  # noqa: F401
 from .timeresp import StepInfo, StepResult, stepinfo  # noqa: F401  (the response itself is timeresp.step: `step` is the Simulation verb)

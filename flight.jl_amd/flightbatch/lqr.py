@@ -11,11 +11,12 @@ LinearizedSS before it goes to the device. A model that exists only to be design
 give it C = I, D = 0, as design_model does."""
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass, replace
 
 import numpy as np
 
-from ._lib import K as _K, check, lib
+from ._lib import K as _K, FlightBatchError, check, lib
 from .linearization import LinearizedSS
 from .lss import LinearWorld, unpack_matrix
 from .modeling import _pd, _pi
@@ -75,3 +76,39 @@ def design_model(A, B, x0=None, x_labels=None, u_labels=None) -> LinearizedSS:
 
 
 NOT_CONVERGED, SINGULAR, NX_MAX = _K["FB_LQR_NOT_CONVERGED"], _K["FB_LQR_SINGULAR"], _K["FB_LQR_NX_MAX"]
+
+
+# ---- the discrete side: lqr(Discrete, Phi, Gamma, Q, R) on a sampled world (include/flightbatch.h: fb_lss_dlqr; kernel: csrc/dlqr_kernels.hpp;
+# docs/design/linearize.md, "Discrete LQR on the device") ---------------------------------------------------------------------------------
+@dataclass
+class DlqrResult:
+    K: np.ndarray        # [N, nu, nx]   u = u0 - K (x - x0), held between samples
+    X: np.ndarray        # [N, nx, nx]   the stabilising solution of the discrete Riccati equation
+    resid: np.ndarray    # [N]           max|Phi'X Phi - X - Phi'X Gamma K + Q| / max(max|Q|, max|X|)
+    iters: np.ndarray    # [N]           doublings taken
+    status: np.ndarray   # [N]           0, or FB_DLQR_NOT_CONVERGED | FB_DLQR_SINGULAR (K, X, resid are NaN there)
+    world: LinearWorld | None = None     # closed=True: the designed loop, a sampled LinearWorld (Phi - Gamma K, C - D K), labels carried over
+
+    @property
+    def success(self) -> np.ndarray:
+        return self.status == 0
+
+
+def dlqr(world: LinearWorld, Q, R, closed: bool = False) -> DlqrResult:
+    """K = lqr(Discrete, Phi, Gamma, Q, R) of every system of a sampled `world` (c2d(w, Ts).world), on its device. Q [nx, nx] and R [nu, nu]
+    are the batch's (1-D: a diagonal). With closed=True the result's `world` is the designed loop as a sampled LinearWorld of its own."""
+    if not isinstance(world, LinearWorld):
+        raise FlightBatchError("dlqr: the world is not a LinearizedSS handle (FB_MODEL_LSS): give it a sampled LinearWorld (c2d(w, Ts).world)")
+    n, nx, nu = world.n, world.nx, world.nu
+    Q, R = _weight(Q, nx, "Q"), _weight(R, nu, "R")
+    Kf, Xf = np.empty(nu * nx * n), np.empty(nx * nx * n)
+    resid, iters, status = np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    h = C.c_void_p()
+    check(lib.fb_lss_dlqr(world._h, _pd(Q.reshape(-1, order="F")), _pd(R.reshape(-1, order="F")), _pd(Kf), _pd(Xf), _pd(resid), _pi(iters), _pi(status),
+                          C.byref(h) if closed else None))
+    w = LinearWorld(_handle=h, _labels=(tuple(world.x_labels), tuple(world.u_labels), tuple(world.y_labels))) if closed else None
+    return DlqrResult(K=unpack_matrix(Kf, nu, nx), X=unpack_matrix(Xf, nx, nx), resid=resid, iters=iters, status=status, world=w)
+
+
+DLQR_NOT_CONVERGED, DLQR_SINGULAR, DLQR_NX_MAX, DLQR_MAX_ITERS = (_K["FB_DLQR_NOT_CONVERGED"], _K["FB_DLQR_SINGULAR"], _K["FB_DLQR_NX_MAX"],
+                                                                  _K["FB_DLQR_MAX_ITERS"])

@@ -413,6 +413,22 @@ function sample_time(w::LinearWorld)
     check(ccall((:fb_lss_sample_time, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), w.handle, ts))
     return ts[]
 end
+"`lqr(Discrete, Phi, Gamma, Q, R)` for every system of a sampled `LinearWorld` (`c2d(w, Ts).world`), on its device: the stabilising solution
+of the discrete Riccati equation by the doubling algorithm and K = inv(R + Gamma' X Gamma) Gamma' X Phi. Q (nx x nx) and R (nu x nu) are
+the batch's, symmetric, R positive definite. Returns k (N x nu x nx), x (N x nx x nx), resid, iters (doublings), status (0, or
+FB_DLQR_NOT_CONVERGED = 1 | FB_DLQR_SINGULAR = 2: K, X and resid are NaN there) and, with `closed = true`, world: the designed loop as a
+sampled `LinearWorld` of its own (Phi - Gamma K in A's place, C - D K in C's), else `nothing`. A continuous world is refused."
+function dlqr(w::LinearWorld, q::Matrix{Float64}, r::Matrix{Float64}; closed::Bool = false)
+    size(q) == (w.nx, w.nx) || throw(DimensionMismatch("Q must be nx x nx"))
+    size(r) == (w.nu, w.nu) || throw(DimensionMismatch("R must be nu x nu"))
+    k = Array{Float64}(undef, w.n, w.nu, w.nx); x = Array{Float64}(undef, w.n, w.nx, w.nx)
+    resid = Vector{Float64}(undef, w.n); iters = Vector{Int32}(undef, w.n); status = Vector{Int32}(undef, w.n)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_dlqr, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32},
+                                            Ptr{Ptr{Cvoid}}), w.handle, q, r, k, x, resid, iters, status, closed ? h : C_NULL))
+    world = closed ? LinearWorld(h[]) : nothing
+    return (; k, x, resid, iters, status, world)
+end
 "`marginplot`'s numbers on the device: gain and phase margins of L = gain (c inv(jωI - A) b + d) of channel (iu, iy) (1-based) of every system
 of a continuous `LinearWorld` under negative unity feedback, from the brackets of the grid `freqs` (rad/s, positive, strictly increasing),
 each refined by bisection. `gain`: `nothing` (ones), a number for the batch or a vector of N. Returns gm (a factor; +Inf without a phase

@@ -503,10 +503,35 @@ int32_t fb_lss_steady(fb_handle lss, const int32_t* iz, int32_t nz, const double
  * from Ts in any bit); fb_f_ode(NULL) refreshes y, fb_f_ode(xdot) is refused (no derivative); fb_lss_get_model returns Phi and Gamma;
  * fb_lss_get_cd is unchanged; fb_lss_stepinfo samples the map at t_k = k Ts (dt must be Ts bit for bit; 0 or a non-finite dt means Ts);
  * fb_lss_set_model, fb_lss_c2d, fb_lqr, fb_pid_metrics, fb_lss_freqresp, fb_lss_poles, fb_lss_connect (either argument),
- * fb_lss_transform and fb_lss_steady are refused ("a continuous-time verb on a sampled model"). */
+ * fb_lss_transform and fb_lss_steady are refused ("a continuous-time verb on a sampled model"); fb_lss_dlqr (below) designs on it. */
 enum { FB_C2D_NOT_FINITE = 1, FB_C2D_RANGE = 2, FB_C2D_SQUARINGS_MAX = 30 };
 int32_t fb_lss_c2d(fb_handle lss, double Ts, int32_t* squarings /* [N] or NULL */, int32_t* status /* [N] or NULL */, fb_handle* out);
 int32_t fb_lss_sample_time(fb_handle h, double* Ts);   /* 0 for a continuous LinearizedSS handle */
+
+/* ---- the discrete LQR of a batch of sampled models (ControlSystems' lqr(Discrete, Phi, Gamma, Q, R), the sampled-data counterpart of the
+ * design scripts' lqr(P, Q, R); the controllers of FP/control.jl run in f_periodic! at dt = 0.02; docs/design/linearize.md, "Discrete LQR on
+ * the device") ----------------------------------------------------------------------------------------------------------------------------
+ * For every system of a SAMPLED FB_MODEL_LSS handle (fb_lss_c2d) with 1 <= nx <= FB_DLQR_NX_MAX and 1 <= nu <= 8, Phi and Gamma read from
+ * the handle's copy of the model: the stabilising solution X of
+ *     X = Phi' X Phi - Phi' X Gamma inv(R + Gamma' X Gamma) Gamma' X Phi + Q
+ * and the gain K = inv(R + Gamma' X Gamma) Gamma' X Phi (u = u0 - K (x - x0)), by the structure-preserving doubling algorithm on
+ * (A, G, H) = (Phi, Gamma inv(R) Gamma', Q): W = I + G H, [V | U] = inv(W) [A | G], H <- H + A' (H V), G <- G + (A U) A', A <- A V, until
+ * max|dH| <= 1e-13 max|H| and max|A| <= 2^-20 (A_k is the closed loop over 2^k samples), at most FB_DLQR_MAX_ITERS doublings; X = (H + H') / 2,
+ * K = inv(R) Gamma' X inv(I + G0 X) Phi. Phi is never inverted (an eigenvalue at 0 is an ordinary input). Q, R and the outputs K, X, iters
+ * and status follow fb_lqr's conventions exactly (one pair of column-major host weights for the batch, symmetry compared exactly, R positive
+ * definite, Q finite; fb_linearize's layout; any output may be NULL). resid [N] = max|Phi' X Phi - X - Phi' X Gamma K + Q| / max(max|Q|,
+ * max|X|); iters [N] = the doublings taken. status [N]: 0; FB_DLQR_NOT_CONVERGED: the bound was reached (a mode on the unit circle that the
+ * weights do not see, or one that no input reaches); FB_DLQR_SINGULAR: a zero or non-finite pivot, or a non-finite A, G, H, K or residual.
+ * A system with a status has K, X and resid = NaN; the call still returns 0 and no other system changes in any bit.
+ * closed (may be NULL: then nothing is allocated): a new sampled FB_MODEL_LSS handle of the same N, nx, nu, ny and Ts that holds the designed
+ * loop with input v, u = v - K (x - x0): Phi - Gamma K in A's place, C - D K in C's; Gamma, D, delta, x0, u0 and y0 copied bit for bit; at
+ * x = x0, u = u0, t = 0; on the source's device, with its stream rule. A system with a status gets Phi - Gamma K and C - D K all NaN.
+ * The source is only read. Refused, with nothing launched and no handle created: a NULL or non-LSS handle, a handle without a model, a
+ * continuous handle (fb_lss_c2d is the way in), nx > FB_DLQR_NX_MAX, a NULL, asymmetric or non-finite Q, a NULL or asymmetric R or one that
+ * is not positive definite. */
+enum { FB_DLQR_NOT_CONVERGED = 1, FB_DLQR_SINGULAR = 2, FB_DLQR_MAX_ITERS = 40, FB_DLQR_NX_MAX = 16 };
+int32_t fb_lss_dlqr(fb_handle lss, const double* Q, const double* R, double* K, double* X, double* resid, int32_t* iters, int32_t* status,
+                    fb_handle* closed /* or NULL */);
 
 /* ---- gain and phase margins of a batch of loops (FA design/robot2d/robot2d_design.ipynb: `marginplot(P_v[:η, :v_ref])` and
  * `marginplot(series(C_η2v, P_v2η))`; docs/design/linearize.md, "Margins on the device") -----------------------------------------------------
