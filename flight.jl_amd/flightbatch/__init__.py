@@ -27,6 +27,7 @@ from .surgery import (TransformResult, SteadyResult, transform, subsystem_world,
 from .c2d import C2dResult, c2d  # noqa: F401  (`c2d` is the verb; the status words are K["FB_C2D_NOT_FINITE"], K["FB_C2D_RANGE"])
 from .timeresp import lsim  # noqa: F401
 from .margins import MarginsResult, margins  # noqa: F401  (`margins` is the verb; the status words are K["FB_MARGINS_*"])
+from .dfreq import DPolesResult, dfreqresp, dmargins, dpoles, ddampreport, default_dgrid  # noqa: F401  (the verbs of a sampled LinearWorld)
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)

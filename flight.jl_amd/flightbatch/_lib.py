@@ -69,6 +69,10 @@ def _load():
         "fb_lss_sample_time": ([H, D], C.c_int32),
         "fb_lss_dlqr": ([H, D, D, D, D, D, I32, I32, C.POINTER(H)], C.c_int32),
         "fb_lss_margins": ([H, C.c_int32, C.c_int32, D, C.c_int32, D, D, I32, D, I32], C.c_int32),
+        "fb_lss_set_sampled": ([H, C.c_double], C.c_int32),
+        "fb_lss_dfreqresp": ([H, C.c_int32, C.c_int32, D, C.c_int32, D, D], C.c_int32),
+        "fb_lss_dmargins": ([H, C.c_int32, C.c_int32, D, C.c_int32, D, D, I32, D, I32], C.c_int32),
+        "fb_lss_dpoles": ([H, D, D, I32, I32], C.c_int32),
         "fb_f_step": ([H], C.c_int32),
         "fb_f_periodic": ([H], C.c_int32),
         "fb_get_outputs": ([H, D], C.c_int32),

@@ -43,7 +43,8 @@ class LinearWorld(BatchedWorld):
     MODEL = "FB_MODEL_LSS"
     _CKPT_ARRAYS = ("x", "u")
 
-    def __init__(self, lss: LinearizedSS | None = None, device: int = 0, _handle=None, _labels=None):
+    def __init__(self, lss: LinearizedSS | None = None, device: int = 0, _handle=None, _labels=None, Ts: float | None = None):
+        """Ts: the LinearizedSS is a sampled model with that sample time, A holding Phi, B Gamma and xdot0 delta (fb_lss_set_sampled)"""
         self._h = C.c_void_p()
         if _handle is not None:      # linear_world(): the library has built the handle on the source's device
             self._h = _handle
@@ -56,6 +57,8 @@ class LinearWorld(BatchedWorld):
             check(lib.fb_lss_create(int(nx), int(nu), int(ny), int(n), int(device), C.byref(self._h)))
             b = pack_model(lss)
             check(lib.fb_lss_set_model(self._h, *[_pd(b[k]) for k in ("xdot0", "x0", "u0", "y0", "A", "B", "C", "D")]))
+            if Ts is not None:
+                check(lib.fb_lss_set_sampled(self._h, float(Ts)))
             self.x_labels, self.u_labels, self.y_labels = tuple(lss.x_labels), tuple(lss.u_labels), tuple(lss.y_labels)
         self.n = int(lib.fb_size(self._h))
         nx, nu, ny = C.c_int32(), C.c_int32(), C.c_int32()

@@ -448,6 +448,39 @@ function margins(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64
     return (; gm = sel[:, 1], wpc = sel[:, 2], pm = sel[:, 3], wgc = sel[:, 4], ms = 1.0 ./ sel[:, 9], wms = sel[:, 10],
             npc = counts[:, 1], ngc = counts[:, 2], status, sel, all = every)
 end
+"Marks a continuous `LinearWorld` that has a model as sampled with sample time `ts`: A's place is read as Phi, B's as Gamma, xdot0's as delta
+(`fb_lss_set_sampled`). The way in for a model given as (Phi, Gamma), such as a loop with a sample of delay (an eigenvalue of Phi at 0)."
+set_sampled!(w::LinearWorld, ts::Real) = (check(ccall((:fb_lss_set_sampled, lib), Cint, (Ptr{Cvoid}, Cdouble), w.handle, Float64(ts))); w)
+"`freqresp(sysd, w)` on the device: P(e^(jωTs)) = c inv(zI - Phi) gamma + d of channel (iu, iy) (1-based) of every system of a sampled
+`LinearWorld` on `freqs` (rad/s, at most π/Ts). Returns a complex N x nw matrix (NaN where a pivot was zero or not finite)."
+function dfreqresp(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64})
+    re = Matrix{Float64}(undef, w.n, length(freqs)); im = Matrix{Float64}(undef, w.n, length(freqs))
+    check(ccall((:fb_lss_dfreqresp, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), re, im))
+    return complex.(re, im)
+end
+"`margins` for a sampled `LinearWorld`: L = gain (c inv(zI - Phi) gamma + d) on z = e^(jωTs), the same arguments and the same named tuple;
+`freqs` in rad/s, strictly increasing, at most π/Ts. The brackets are refined by bisecting the arc of the unit circle. A phase crossing at
+the Nyquist frequency itself is not bracketed. `dpoles` of the closed loop says whether it is stable."
+function dmargins(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64}; gain = nothing, all::Bool = false)
+    g = gain === nothing ? nothing : (gain isa Real ? fill(Float64(gain), w.n) : Vector{Float64}(gain))
+    g === nothing || length(g) == w.n || throw(DimensionMismatch("dmargins: gain has $(length(g)) entries for $(w.n) systems"))
+    sel = Matrix{Float64}(undef, w.n, 10); counts = Matrix{Int32}(undef, w.n, 2); status = Vector{Int32}(undef, w.n)
+    every = all ? Array{Float64}(undef, w.n, 8, 6) : nothing
+    check(ccall((:fb_lss_dmargins, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), g === nothing ? C_NULL : g, sel, counts, every === nothing ? C_NULL : every, status))
+    return (; gm = sel[:, 1], wpc = sel[:, 2], pm = sel[:, 3], wgc = sel[:, 4], ms = 1.0 ./ sel[:, 9], wms = sel[:, 10],
+            npc = counts[:, 1], ngc = counts[:, 2], status, sel, all = every)
+end
+"`poles(sysd)` on the device: the eigenvalues z of Phi of every system of a sampled `LinearWorld`, with `poles`' outputs, order (ascending
+|z|) and status. `damp`'s reading is s = log(z) / Ts, wn = |s|, zeta = -cos(arg s); stable where every |z| < 1."
+function dpoles(w::LinearWorld)
+    re = Matrix{Float64}(undef, w.n, w.nx); im = Matrix{Float64}(undef, w.n, w.nx)
+    iters = Vector{Int32}(undef, w.n); status = Vector{Int32}(undef, w.n)
+    check(ccall((:fb_lss_dpoles, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}), w.handle, re, im, iters, status))
+    return (; re, im, iters, status)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

@@ -570,6 +570,40 @@ int32_t fb_lss_margins(fb_handle lss, int32_t iu, int32_t iy, const double* w, i
                        double* sel /* [10 x N] */, int32_t* counts /* [2 x N] */, double* all /* [6 x KMAX x N] or NULL */,
                        int32_t* status /* [N] */);
 
+/* ---- sampled loops: frequency response, margins and poles of a batch of sampled models (ControlSystems' freqresp, margin, poles and damp on a
+ * discrete system; the controllers of FP/control.jl run in f_periodic! at dt = 0.02 on gains designed in continuous time;
+ * docs/design/linearize.md, "Sampled loops on the device") -----------------------------------------------------------------------------------
+ * The three d verbs take a SAMPLED FB_MODEL_LSS handle (fb_lss_c2d, fb_lss_dlqr's closed, fb_lss_set_sampled) with a model and
+ * 1 <= nx <= 32, read the handle's copy of the model (Phi, Gamma in A's and B's places), run on its stream and change nothing on it. A
+ * continuous handle is refused ("a discrete-time verb on a continuous model"), as a NULL or non-LSS handle and a handle without a model are;
+ * every refusal is decided before anything is launched. fb_lss_freqresp, fb_lss_margins and fb_lss_poles keep refusing a sampled handle.
+ * fb_lss_set_sampled: marks a continuous handle that has a model as sampled with sample time Ts: the block in A's place is read as Phi, B's
+ * as Gamma, xdot0's as delta (x+ = x0 + Phi (x - x0) + Gamma (u - u0) + delta), where fb_lss_c2d leaves them. The handle's dt becomes Ts;
+ * state, inputs and clock are untouched. From then on it is a sampled handle under every verb, exactly like a result of fb_lss_c2d. This is
+ * the way in for a model that is no zero-order hold of a continuous one: a loop with a sample of delay has a Phi with an eigenvalue at 0.
+ * Refused: a NULL or non-LSS handle, a handle without a model, a handle that is already sampled, Ts not finite or <= 0.
+ * fb_lss_dfreqresp: P(e^(j w Ts)) = c inv(z I - Phi) gamma + d of channel (iu, iy) on w [nw], 1 <= nw <= 1024, into re, im [nw x N] (system
+ * index fastest; NaN where a pivot was zero or not finite), fb_lss_freqresp's layout. The host forms theta_k = w_k Ts, cos theta_k and
+ * sin theta_k; no trigonometric function is evaluated on the device. Launched in slices of whole frequencies of at most 2^25 one-wave
+ * workgroups, so N nw is bounded by memory only. Refused besides: iu or iy out of range, a NULL w, re or im, nw out of range, a grid entry
+ * that is not positive and finite, theta_k > pi ("above the Nyquist frequency pi/Ts").
+ * fb_lss_dmargins: fb_lss_margins (above) for L(z) = gain (c inv(z I - Phi) gamma + d) on the unit circle: its signature, row layouts,
+ * bracket predicates, selection rules, status bits and FB_MARGINS_KMAX, frequencies in and out in rad/s. What differs: a bracket is a pair
+ * of points of the circle and is refined by bisecting the arc, mid = (z_lo + z_hi) / |z_lo + z_hi|, (each component held between the ends' where it is
+ * monotone along the arc), until mid equals an end in both components or after 63 halvings; the crossing is z* = the final z_lo with L* = L(z*), and w* = atan2(Im z*, Re z*) / Ts is computed by the
+ * host side of this call, beside gm, pm and smin. Stage 1 is fb_lss_dfreqresp's kernel on the grid (the same bits), in its slices.
+ * Refused besides: what fb_lss_dfreqresp refuses, nw outside [2, 1024], a NULL sel, counts or status, a grid whose theta does not strictly
+ * increase, N nw above 2^31 - 1. Limit: a phase crossing at the Nyquist frequency itself is not bracketed (L is real there: Im L does not
+ * change sign inside the grid); the limits of fb_lss_margins hold as well.
+ * fb_lss_dpoles: the eigenvalues of Phi of every system, with fb_lss_poles' outputs, order (ascending |z|) and status bits (its kernel). The
+ * z-plane reading (s = log(z) / Ts, natural frequency, damping) is host arithmetic (flightbatch/dfreq.py). */
+int32_t fb_lss_set_sampled(fb_handle lss, double Ts);
+int32_t fb_lss_dfreqresp(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double* re, double* im);
+int32_t fb_lss_dmargins(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, const double* gain /* [N] or NULL */,
+                        double* sel /* [10 x N] */, int32_t* counts /* [2 x N] */, double* all /* [6 x KMAX x N] or NULL */,
+                        int32_t* status /* [N] */);
+int32_t fb_lss_dpoles(fb_handle lss, double* re, double* im, int32_t* iters, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
