@@ -560,16 +560,30 @@ int32_t fb_set_stream(fb_handle h, void* hip_stream) {
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     return 0;
 }
+// Nothing is copied in either direction: the handle holds what the buffer it is given holds. A refusal queues nothing and leaves the handle as
+// it was. Attaching the pointers that are attached already is how a caller says "I wrote x or s on the device": the carried derivative is
+// dropped and the stream is synchronised.
 int32_t fb_attach_state(fb_handle h, void* x_dev, void* s_dev) {
-    if (h) fsal_invalidate(h);
     if (!h) return fail("null handle");
     if (h->model == FB_MODEL_ROBOT2D) return fail("fb_attach_state: not supported for Robot2D");
     if (is_lss(h)) return lss_refuse("fb_attach_state", "its state rows are the handle's own");
-    if ((x_dev == nullptr) != (s_dev == nullptr)) return fail("x_dev and s_dev must both be given or both be NULL");
+    if ((x_dev == nullptr) != (s_dev == nullptr)) return fail("fb_attach_state: x_dev and s_dev must both be given or both be NULL");
+    // (the kernels address the rows one element per lane, so an element's alignment is all a view into a larger allocation has to keep)
+    if ((uintptr_t)x_dev % sizeof(double)) return fail("fb_attach_state: x_dev must be 8-byte aligned (rows of doubles)");
+    if ((uintptr_t)s_dev % sizeof(int32_t)) return fail("fb_attach_state: s_dev must be 4-byte aligned (rows of int32)");
+    fsal_invalidate(h);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->x = x_dev ? (double*)x_dev : h->x_own;
     h->s = s_dev ? (int32_t*)s_dev : h->s_own;
+    // The kinematic rows ECEF and NED leave unused are not idle: every stepping kernel loads all FB_NX rows, integrates them with a zero
+    // derivative, tests them for finiteness with the rest (FB_ST_NAN) and stores them back. The handle's own rows are zero from fb_create on;
+    // a caller's buffer (torch.empty) holds anything, and fb_set_state writes the rows in use only — so they are zeroed here.
+    if (x_dev && h->kin != FB_KIN_WA) {
+        const int first = FB_X_Q_WB + (h->kin == FB_KIN_ECEF ? 8 : 6), count = FB_X_Q_WB + 9 - first;
+        HIPCHK(hipMemsetAsync(h->x + (int64_t)first * h->n, 0, sizeof(double) * count * h->n, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     return 0;
 }
 

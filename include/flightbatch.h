@@ -252,14 +252,33 @@ int64_t fb_size(fb_handle h);
 /* per-model array sizes: continuous+discrete real state, int state, real inputs, output record (0 where absent) */
 int32_t fb_dims(fb_handle h, int32_t* nx, int32_t* ns, int32_t* nu, int32_t* ny);
 
-/* Run on an externally created HIP stream (hipStream_t passed as void*); NULL = the handle's own stream. */
+/* Run on an externally created HIP stream (hipStream_t passed as void*). Every launch and copy of the handle is queued on that stream and
+ * on no other: work the caller queued there before an fb_step is seen by the step, work queued behind it sees the step's result, with no
+ * host synchronisation between. NULL = the handle's OWN stream (a non-blocking one it created), not HIP's null stream — a torch host whose
+ * current stream is the default one (cuda_stream == 0) gets the handle's own stream and has to synchronise, or make a side stream current.
+ * The call waits for everything queued on the stream the handle leaves (the caller's work on it included) before it switches; the clock,
+ * the state and everything else the handle holds stay. Handles made FROM this one (fb_lss_from_linearization, fb_lss_c2d, ...) run on the
+ * caller's stream it is on. The stream must outlive its use: switch back (NULL) or destroy the handle before the stream is destroyed. */
 int32_t fb_set_stream(fb_handle h, void* hip_stream);
 /* Use caller-owned DEVICE memory for x and s [N x FB_NS int32] (e.g. a torch tensor's data_ptr), so collectives can run
- * on the state without a host round trip. NULL restores the handle's own buffers. The buffer holds the DEVICE layout:
- * [N x FB_NX] doubles for every Cessna172Sv0 mechanisation (ECEF / NED: their 8 / 6 kinematic states in rows 12.., the
- * remaining kinematic rows zero, then w_eb_b, v_eb_b in rows 21-26) and [N x FB_X2_NX] for every Cessna172Xv2 mechanisation
- * with the Sv0 rows first (laid out as just described) and the seven actuator positions in rows 27-33; fb_get_state /
- * fb_set_state present the reference's order and row count. */
+ * on the state without a host round trip. NULL, NULL restores the handle's own buffers. The buffer holds the DEVICE layout, aircraft
+ * index fastest: [N x FB_NX] doubles for every Cessna172Sv0 mechanisation — rows 0-11 as in the C ABI's state; the mechanisation's
+ * kinematic states from row 12 on in the C ABI's order (WA 9, ECEF 8, NED 6); then, always in rows 21-26, w_eb_b and v_eb_b — and
+ * [N x FB_X2_NX] for every Cessna172Xv2 mechanisation, with the Sv0 rows first (laid out as just described: the C ABI's rows below
+ * FB_X2_ACT and from FB_X2_KIN on) and the seven actuator positions (the C ABI's rows FB_X2_ACT ..) in rows 27-33. fb_get_state /
+ * fb_set_state present the reference's order and row count on an attached buffer as on the handle's own.
+ *   The rows a mechanisation does not use (ECEF: row 20, NED: rows 18-20) may hold anything when the buffer is attached: the call zeroes
+ *   them. They are not idle — the kernels carry them through every launch and test them for finiteness with the rest — so they must stay
+ *   zero afterwards; fb_set_state does not write them.
+ *   Nothing is copied, by attach or by detach: after an attach the handle's state is what the caller's buffer holds (apart from the zeroed
+ *   rows); after fb_attach_state(h, NULL, NULL) it is what the handle's own buffers held before the attach, which no launch has written
+ *   meanwhile. The clock, the step count, the status words, the termination record, the inputs and the control-law record stay as they are.
+ *   The call synchronises the handle's stream (what is queued there is done, and so is the zeroing, when it returns) and drops the derivative Cessna172Xv2 carries from one launch to
+ *   the next, like every call that changes x. A caller who writes x or s in the attached buffer ITSELF (a copy, a collective, a torch
+ *   kernel) announces that by calling fb_attach_state again with the same pointers, before the next fb_step; without the call a
+ *   Cessna172Xv2 may step from the derivative of the state it had.
+ *   x_dev must be 8-byte aligned and s_dev 4-byte aligned (a view into a larger tensor is fine: every access is one element wide); x
+ *   without s, s without x, a misaligned pointer, a Robot2D or a LinearizedSS handle are refused, and a refusal changes nothing. */
 int32_t fb_attach_state(fb_handle h, void* x_dev, void* s_dev);
 
 /* Lookup tables: what the reference builds at construction time (Appendix B of SURVEY.md). */

@@ -213,6 +213,68 @@ def library_kernels(tmp_path_factory):
     return out
 
 
+# ---- 3b. aircraft trimmed over a runway: the batches of the air / ground hand-over tests -------------------------------------------------------
+def band_scenario(fb, N0, n, h_trn, band, s_reverse, s_mirror, seed=7):
+    """tests/test_gpu_launch_edges.py's batch: trim parameters, groups and control-law inputs of n Cessna172Xv2 around the `band` metres over
+    a runway at h_trn (N0: the geoid height there), drawn once, the same for every case"""
+    K = fb.K
+    N = n
+    rng = np.random.default_rng(seed)
+    grp = rng.integers(0, 3, N)
+    ga, gb, gc = grp == 0, grp == 1, grp == 2
+    lev = ga & (rng.random(N) < 0.5)
+    rev = ga & ~lev
+    clr0 = np.where(lev, rng.uniform(12, 30, N), np.where(rev, rng.uniform(10.5, 13, N), np.where(gb, rng.uniform(9.0, 11.0, N), rng.uniform(4, 9, N))))
+    gam = np.where(lev, -rng.uniform(0.03, 0.06, N), np.where(rev, -rng.uniform(0.04, 0.06, N), np.where(gb, 0.0, rng.uniform(0.02, 0.05, N))))
+    tp = fb.TrimParameters(EAS=rng.uniform(42.0, 55.0, N), h_e=h_trn + N0 + clr0, ψ_nb=rng.uniform(-np.pi, np.pi, N), γ_wb_n=gam)
+    clm = np.where(lev, -rng.uniform(1.5, 3.5, N), np.where(rev, -rng.uniform(2.0, 3.0, N), rng.uniform(1.5, 3.0, N)))
+    clm_up = rng.uniform(3.0, 5.0, N)
+    dh = np.where(lev, rng.uniform(5, 8, N), band + rng.uniform(-1, 1, N))
+
+    def set_cu(cu):
+        cu[K["FB_CU_LON_MODE_REQ"]] = np.where(lev | gb, float(fb.ModeControlLon.EAS_alt), float(fb.ModeControlLon.EAS_clm))
+        cu[K["FB_CU_LAT_MODE_REQ"]] = float(fb.ModeControlLat.φ_β)
+        cu[K["FB_CU_CLM_REF"]] = clm
+        cu[K["FB_CU_H_REF"]] = h_trn + N0 + dh
+        cu[K["FB_CU_EAS_REF"]] = tp.EAS
+        return cu
+
+    def write(cu, step):
+        """the host's write between two fb.step calls, on the device and on the oracle alike"""
+        if step == s_reverse:
+            cu[K["FB_CU_CLM_REF"], rev] = clm_up[rev]
+        if step in s_mirror:
+            cu[K["FB_CU_H_REF"], gb] = 2 * (h_trn + N0 + band) - cu[K["FB_CU_H_REF"], gb]
+        return cu
+    return tp, dict(a=ga, b=gb, c=gc), set_cu, write
+
+
+RUNWAY_H_TRN, RUNWAY_BAND = 120.0, 10.0
+
+
+def runway_batch(fb, N0, n, seed=357):
+    """n aircraft trimmed over the runway of band_scenario, three groups mixed within every wave: (air) level at 40-100 m, airborne throughout;
+    (band) descending from 10.5-13 m through the band's edge; (gnd) sinking at 1-2 m/s from 2.3-3.8 m, onto the wheels within the first
+    second or two. Returns the trim parameters, the groups and set_cu (Cessna172Xv2: the autopilot holds each group to its path)."""
+    K = fb.K
+    rng = np.random.default_rng(seed)
+    grp = rng.integers(0, 3, n)
+    air, bnd, gnd = grp == 0, grp == 1, grp == 2
+    clr0 = np.where(air, rng.uniform(40, 100, n), np.where(bnd, rng.uniform(10.5, 13, n), rng.uniform(2.3, 3.8, n)))
+    gam = np.where(air, 0.0, np.where(bnd, -rng.uniform(0.04, 0.06, n), -rng.uniform(0.02, 0.04, n)))
+    tp = fb.TrimParameters(EAS=rng.uniform(42.0, 55.0, n), h_e=RUNWAY_H_TRN + N0 + clr0, ψ_nb=rng.uniform(-np.pi, np.pi, n), γ_wb_n=gam)
+    clm = np.where(bnd, -rng.uniform(2.0, 3.0, n), -rng.uniform(1.0, 2.0, n))
+
+    def set_cu(cu):
+        cu[K["FB_CU_LON_MODE_REQ"]] = np.where(air, float(fb.ModeControlLon.EAS_alt), float(fb.ModeControlLon.EAS_clm))
+        cu[K["FB_CU_LAT_MODE_REQ"]] = float(fb.ModeControlLat.φ_β)
+        cu[K["FB_CU_CLM_REF"]] = clm
+        cu[K["FB_CU_H_REF"]] = RUNWAY_H_TRN + N0 + clr0
+        cu[K["FB_CU_EAS_REF"]] = tp.EAS
+        return cu
+    return tp, dict(air=air, band=bnd, gnd=gnd), set_cu
+
+
 # ---- 4. scenario tables: the two ways to run one -------------------------------------------------------------------------------------------
 def same(a, b):
     return np.array_equal(a, b, equal_nan=True)
@@ -403,3 +465,117 @@ def exchange(name):
     exchange it got."""
     import contextlib
     return contextlib.contextmanager(_exchange)(name)
+
+
+# ---- 7. a caller's device memory and streams: ctypes on the HIP runtime the library is linked against (no torch in the pytest process) ---------
+HIP_H2D, HIP_D2H, HIP_D2D = 1, 2, 3          # hipMemcpyKind
+HIP_NOT_READY = 600                          # hipErrorNotReady
+GUARD_BYTE = 0xA5
+
+
+class Hip:
+    """the few runtime calls a host that owns its state buffers and its stream makes; every call is checked (query() returns the code)"""
+    def __init__(self):
+        L = self.lib = C.CDLL("libamdhip64.so")
+        VP, SZ = C.c_void_p, C.c_size_t
+        for name, args in (("hipMalloc", [C.POINTER(VP), SZ]), ("hipFree", [VP]), ("hipMemcpy", [VP, VP, SZ, C.c_int]),
+                           ("hipMemcpyAsync", [VP, VP, SZ, C.c_int, VP]), ("hipMemset", [VP, C.c_int, SZ]),
+                           ("hipStreamCreateWithFlags", [C.POINTER(VP), C.c_uint]), ("hipStreamDestroy", [VP]), ("hipStreamSynchronize", [VP]),
+                           ("hipEventCreate", [C.POINTER(VP)]), ("hipEventRecord", [VP, VP]), ("hipEventQuery", [VP]), ("hipEventDestroy", [VP]),
+                           ("hipDeviceSynchronize", [])):
+            f = getattr(L, name)
+            f.argtypes, f.restype = args, C.c_int
+
+    def _ok(self, rc, what):
+        assert rc == 0, f"{what} failed with HIP error {rc}"
+
+    def malloc(self, nbytes):
+        p = C.c_void_p()
+        self._ok(self.lib.hipMalloc(C.byref(p), nbytes), "hipMalloc")
+        return p.value
+
+    def free(self, p):
+        self._ok(self.lib.hipFree(p), "hipFree")
+
+    def memset(self, p, byte, nbytes):
+        self._ok(self.lib.hipMemset(p, byte, nbytes), "hipMemset")
+
+    def upload(self, dst, a):
+        a = np.ascontiguousarray(a)
+        self._ok(self.lib.hipMemcpy(dst, a.ctypes.data_as(C.c_void_p), a.nbytes, HIP_H2D), "hipMemcpy (to the device)")
+
+    def download(self, src, shape, dtype):
+        out = np.empty(shape, dtype=dtype)
+        self._ok(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), src, out.nbytes, HIP_D2H), "hipMemcpy (from the device)")
+        return out
+
+    def copy(self, dst, src, nbytes):
+        """device to device on the null stream, complete on return"""
+        self._ok(self.lib.hipMemcpy(dst, src, nbytes, HIP_D2D), "hipMemcpy (device to device)")
+        self.device_sync()
+
+    def copy_async(self, dst, src, nbytes, stream):
+        self._ok(self.lib.hipMemcpyAsync(dst, src, nbytes, HIP_D2D, stream), "hipMemcpyAsync")
+
+    def stream(self):
+        s = C.c_void_p()
+        self._ok(self.lib.hipStreamCreateWithFlags(C.byref(s), 1), "hipStreamCreateWithFlags(hipStreamNonBlocking)")
+        return s.value
+
+    def stream_destroy(self, s):
+        self._ok(self.lib.hipStreamDestroy(s), "hipStreamDestroy")
+
+    def stream_sync(self, s):
+        self._ok(self.lib.hipStreamSynchronize(s), "hipStreamSynchronize")
+
+    def device_sync(self):
+        self._ok(self.lib.hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+    def event(self, stream):
+        """a new event recorded on `stream` behind what is queued there"""
+        e = C.c_void_p()
+        self._ok(self.lib.hipEventCreate(C.byref(e)), "hipEventCreate")
+        self._ok(self.lib.hipEventRecord(e.value, stream), "hipEventRecord")
+        return e.value
+
+    def query(self, e):
+        """0: everything in front of the event is done; HIP_NOT_READY: not yet"""
+        rc = self.lib.hipEventQuery(e)
+        assert rc in (0, HIP_NOT_READY), f"hipEventQuery failed with HIP error {rc}"
+        return rc
+
+    def event_destroy(self, e):
+        self._ok(self.lib.hipEventDestroy(e), "hipEventDestroy")
+
+
+class GuardedRows:
+    """[rows x n] elements of `dtype` in device memory that the CALLER owns: one allocation with a guard row of n elements in front of the rows
+    and one behind them, every byte outside the rows GUARD_BYTE. `offset` bytes shift the rows inside the allocation (a view into a larger
+    tensor: 8-byte aligned doubles, 4-byte aligned int32). The rows start out as `fill`."""
+    def __init__(self, hip, rows, n, dtype, offset=0, fill=0):
+        self.hip, self.rows, self.n, self.dtype = hip, rows, n, np.dtype(dtype)
+        self.nbytes = rows * n * self.dtype.itemsize
+        self.lead = n * self.dtype.itemsize + offset
+        self.total = self.nbytes + 2 * n * self.dtype.itemsize + 16
+        assert 0 <= offset <= 16
+        self.base = hip.malloc(self.total)
+        hip.memset(self.base, GUARD_BYTE, self.total)
+        self.ptr = self.base + self.lead
+        self.write(np.full((rows, n), fill, dtype=self.dtype))
+
+    def write(self, a):
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        assert a.shape == (self.rows, self.n)
+        self.hip.upload(self.ptr, a)
+
+    def read(self):
+        return self.hip.download(self.ptr, (self.rows, self.n), self.dtype)
+
+    def guards_intact(self):
+        raw = self.hip.download(self.base, (self.total,), np.uint8)
+        return bool((raw[:self.lead] == GUARD_BYTE).all() and (raw[self.lead + self.nbytes:] == GUARD_BYTE).all())
+
+    def free(self):
+        if self.base:
+            self.hip.free(self.base)
+            self.base = 0

@@ -30,7 +30,7 @@ import numpy as np
 import pytest
 
 from oracle_binding import OracleX
-from support import abi_to_oracle_rows, digest, geoid, state_scale, stepper
+from support import abi_to_oracle_rows, band_scenario, digest, geoid, state_scale, stepper
 
 pytestmark = pytest.mark.gpu
 
@@ -44,36 +44,8 @@ WRITES = sorted((S_REVERSE,) + S_MIRROR)
 
 
 def scenario(fb, N0):
-    """trim parameters, groups and control-law inputs (drawn once, the same for every case)"""
-    K = fb.K
-    rng = np.random.default_rng(7)
-    grp = rng.integers(0, 3, N)
-    ga, gb, gc = grp == 0, grp == 1, grp == 2
-    lev = ga & (rng.random(N) < 0.5)
-    rev = ga & ~lev
-    clr0 = np.where(lev, rng.uniform(12, 30, N), np.where(rev, rng.uniform(10.5, 13, N), np.where(gb, rng.uniform(9.0, 11.0, N), rng.uniform(4, 9, N))))
-    gam = np.where(lev, -rng.uniform(0.03, 0.06, N), np.where(rev, -rng.uniform(0.04, 0.06, N), np.where(gb, 0.0, rng.uniform(0.02, 0.05, N))))
-    tp = fb.TrimParameters(EAS=rng.uniform(42.0, 55.0, N), h_e=H_TRN + N0 + clr0, ψ_nb=rng.uniform(-np.pi, np.pi, N), γ_wb_n=gam)
-    clm = np.where(lev, -rng.uniform(1.5, 3.5, N), np.where(rev, -rng.uniform(2.0, 3.0, N), rng.uniform(1.5, 3.0, N)))
-    clm_up = rng.uniform(3.0, 5.0, N)
-    dh = np.where(lev, rng.uniform(5, 8, N), BAND + rng.uniform(-1, 1, N))
-
-    def set_cu(cu):
-        cu[K["FB_CU_LON_MODE_REQ"]] = np.where(lev | gb, float(fb.ModeControlLon.EAS_alt), float(fb.ModeControlLon.EAS_clm))
-        cu[K["FB_CU_LAT_MODE_REQ"]] = float(fb.ModeControlLat.φ_β)
-        cu[K["FB_CU_CLM_REF"]] = clm
-        cu[K["FB_CU_H_REF"]] = H_TRN + N0 + dh
-        cu[K["FB_CU_EAS_REF"]] = tp.EAS
-        return cu
-
-    def write(cu, step):
-        """the host's write between two fb.step calls, on the device and on the oracle alike"""
-        if step == S_REVERSE:
-            cu[K["FB_CU_CLM_REF"], rev] = clm_up[rev]
-        if step in S_MIRROR:
-            cu[K["FB_CU_H_REF"], gb] = 2 * (H_TRN + N0 + BAND) - cu[K["FB_CU_H_REF"], gb]
-        return cu
-    return tp, dict(a=ga, b=gb, c=gc), set_cu, write
+    """trim parameters, groups and control-law inputs (drawn once, the same for every case): support.band_scenario"""
+    return band_scenario(fb, N0, N, H_TRN, BAND, S_REVERSE, S_MIRROR)
 
 
 _ORACLE = {}   # (ratio, digest of the start state) -> oracle run with its coverage record
