@@ -31,3 +31,5 @@ from .dfreq import DPolesResult, dfreqresp, dmargins, dpoles, ddampreport, defau
 from . import pidopt  # noqa: F401
 from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult, build_pid, freqresp, pid_metrics, optimize_pid,  # noqa: F401
                      check_results)
+from . import dpid  # noqa: F401
+from .dpid import DPIDMetricsResult, build_dpid, dpid_metrics, optimize_dpid  # noqa: F401  (the sampled law on a sampled LinearWorld)

@@ -11,8 +11,8 @@ csrc/pid_kernels.hpp; docs/design/linearize.md, "PID loop design on the device")
     check_results(results, thresholds)    :130-153                     check_results(results, thresholds)
 
 The plant of every call is channel (u, y) of each system of a LinearWorld. What differs from the reference: its step() picks the sample
-time and discretises exactly, here the loop is advanced by RK4 with the caller's dt (default: min τ_f / 10; the exact map is flightbatch.c2d, which fb_pid_metrics
-does not use yet); its hinfnorm2 finds the exact
+time and discretises exactly, here the loop is advanced by RK4 with the caller's dt (default: min τ_f / 10; the exact map is flightbatch.c2d; the metrics on it, under the
+sampled PID law, are flightbatch.dpid's); its hinfnorm2 finds the exact
 peak of the sensitivity and is infinite for an unstable loop, here Ms is the peak over the frequency grid `w` and an unstable loop shows
 as DIVERGED; NLopt's GN_DIRECT_L and LN_BOBYQA are not restated: the search is a bounded pattern search, every system of the batch running
 its own, all of them in one fb_pid_metrics launch per iteration."""

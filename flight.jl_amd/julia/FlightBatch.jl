@@ -481,6 +481,24 @@ function dpoles(w::LinearWorld)
     check(ccall((:fb_lss_dpoles, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}), w.handle, re, im, iters, status))
     return (; re, im, iters, status)
 end
+"`optimize_PID`'s metrics under the sampled PID law (`f_periodic!` of `PID` every Ts: backward-Euler integrator and filtered derivative,
+output clamp, integrator halted while clamped) for every (system, candidate) pair of a sampled `LinearWorld`, channel (iu, iy) (1-based).
+`pid` is N x m x 4 (k_p, k_i, k_d, τ_f >= 0); `bounds` is `nothing` or N x m x 2 (lo, hi; either may be infinite; a finite bound needs d = 0);
+`freqs` in rad/s, at most π/Ts. Returns metrics (N x m x 5: Ms, ie, ef, iu, up; Ms is the linear law's, on the grid), cost, status (0, or
+FB_DPID_DIVERGED = 1, FB_DPID_SINGULAR = 2, FB_DPID_DIRECT = 4) and counts (N x m x 2: ticks clamped, ticks with the integrator halted)."
+function dpid_metrics(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Float64}, t_sim::Real, pid::Array{Float64, 3};
+                      weights::Union{Vector{Float64}, Nothing} = nothing, bounds::Union{Array{Float64, 3}, Nothing} = nothing)
+    size(pid, 1) == w.n && size(pid, 3) == 4 || throw(DimensionMismatch("pid must be N x m x 4"))
+    m = size(pid, 2)
+    bounds === nothing || size(bounds) == (w.n, m, 2) || throw(DimensionMismatch("bounds must be N x m x 2"))
+    metrics = Array{Float64}(undef, w.n, m, 5); cost = Matrix{Float64}(undef, w.n, m)
+    counts = Array{Int32}(undef, w.n, m, 2); status = Matrix{Int32}(undef, w.n, m)
+    check(ccall((:fb_lss_dpid_metrics, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                                                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}),
+                w.handle, iu - 1, iy - 1, freqs, length(freqs), t_sim, weights === nothing ? C_NULL : weights, pid,
+                bounds === nothing ? C_NULL : bounds, m, metrics, cost, counts, status))
+    return (; metrics, cost, status, counts)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

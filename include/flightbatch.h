@@ -623,6 +623,43 @@ int32_t fb_lss_dmargins(fb_handle lss, int32_t iu, int32_t iy, const double* w, 
                         int32_t* status /* [N] */);
 int32_t fb_lss_dpoles(fb_handle lss, double* re, double* im, int32_t* iters, int32_t* status);
 
+/* ---- discrete PID design: the metrics of optimize_PID under the sampled law on a batch of sampled models (f_periodic! of PID,
+ * FP/control.jl:431-471, the law Cessna172Xv2 and Robot2D run every dt = 0.02; FA design/pidopt.jl: Metrics :36-64, cost :66-70;
+ * docs/design/linearize.md, "Discrete PID design on the device") ----------------------------------------------------------------------------
+ * The plant is channel (iu, iy) of each system of a SAMPLED FB_MODEL_LSS handle with a model and 1 <= nx <= FB_DPID_NX_MAX, in deviation
+ * coordinates: Phi, gamma = Gamma[:, iu], c = C[iy, :], d = D[iy, iu] (delta, x0, u0, y0 play no part). pid [4 x m x N], 1 <= m <= 64:
+ * (k_p, k_i, k_d, tau_f) of candidate j of system i at pid[(f m + j) N + i] (fb_pid_metrics' layout), tau_f >= 0 (0: the plain backward
+ * difference); alpha = 1 / (tau_f + Ts). bounds: NULL (no bounds) or [2 x m x N], lo then hi, lo < hi, either may be infinite.
+ * Unit step of the reference from rest, ticks k = 0 .. N_t, N_t = round(t_sim / Ts), 1 <= N_t <= 200000, xi_-1 = eta_-1 = 0, sat_-1 = 0:
+ *   s_k = c x_k
+ *   a pair without a finite bound (the algebraic loop through d is solved: the loop is P(z) C(z) with fb_lss_dfreqresp's P):
+ *       Dc = k_p + Ts k_i + alpha k_d,  u_k = (Dc (1 - s_k) + xi_k-1 - alpha eta_k-1) / (1 + d Dc),  e_k = 1 - s_k - d u_k,
+ *       xi_k = xi_k-1 + Ts k_i e_k
+ *   a pair with a finite bound (d must be exactly 0): e_k = 1 - s_k; halted_k = e_k sat_k-1 > 0; xi_k = xi_k-1 when halted, else
+ *       xi_k-1 + Ts k_i e_k; free_k = k_p e_k + xi_k + alpha (k_d e_k - eta_k-1); u_k = clamp(free_k, lo, hi);
+ *       sat_k = (free_k >= hi) - (free_k <= lo)
+ *   both: eta_k = alpha tau_f eta_k-1 + Ts alpha k_d e_k;  y_k = s_k + d u_k;  x_k+1 = Phi x_k + gamma u_k
+ * (a backward-Euler integrator and filtered derivative, an output clamp, an integrator that halts while the output is clamped and the error
+ * pushes further into the bound; the reference block's sat_ext input and reference weights are 0 and 1.)
+ * metrics [5 x m x N] (may be NULL), cost [m x N], status [m x N], weights [5] or NULL: fb_pid_metrics' definitions, row order (Ms, ie, ef,
+ * iu, up) and layouts on the samples y_k, u_k, t_N = N_t Ts. Ms = min(1e3, max over the grid of 1 / |1 + P(z_j) C(z_j)|), z_j = e^(j w_j Ts),
+ * C(z) = k_p + k_i Ts z / (z - 1) + k_d alpha (z - 1) / (z - alpha tau_f): the LINEAR law's sensitivity. The bounds play no part in Ms.
+ * counts [2 x m x N] (may be NULL): the ticks k = 0 .. N_t with sat_k != 0, then the ticks with the integrator halted.
+ * The grid w [nw] follows fb_lss_dfreqresp's rules (1 <= nw <= 1024, positive, finite, w Ts <= pi as the host computes it; the host forms
+ * cos and sin, no trigonometric function is evaluated on the device); P on the grid is that verb's kernel, in its slices.
+ * status: 0; FB_DPID_DIVERGED: a sample y_k or u_k was not finite or beyond 1e12 (ie, ef, iu, up and cost are +Inf, Ms is the grid's);
+ * FB_DPID_SINGULAR: a zero or non-finite pivot at some grid point, or 1 + d Dc zero or not finite (the metrics are NaN, cost +Inf, counts 0);
+ * FB_DPID_DIRECT: a finite bound on a system with d != 0 (the metrics are NaN, cost +Inf, counts 0). The call returns 0 in all three cases
+ * and no other pair changes in any bit. Reads the handle's copy of the model, runs on its stream and changes nothing on the handle.
+ * Refused, with nothing launched: a NULL or non-LSS handle, a handle without a model, a continuous handle ("a discrete-time verb on a
+ * continuous model"), nx > FB_DPID_NX_MAX, m outside 1 .. 64, iu or iy out of range, a grid fb_lss_dfreqresp refuses, a negative or
+ * non-finite weight or weights that sum to zero, t_sim not finite or N_t outside 1 .. 200000, tau_f < 0 or not finite, lo >= hi or a NaN
+ * bound, a NULL pid, cost or status. fb_pid_metrics keeps refusing a sampled handle. */
+enum { FB_DPID_DIVERGED = 1, FB_DPID_SINGULAR = 2, FB_DPID_DIRECT = 4, FB_DPID_NX_MAX = 31 };
+int32_t fb_lss_dpid_metrics(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double t_sim, const double* weights,
+                            const double* pid, const double* bounds /* [2 x m x N] or NULL */, int32_t m, double* metrics, double* cost,
+                            int32_t* counts /* [2 x m x N] or NULL */, int32_t* status);
+
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
 int32_t fb_f_ode(fb_handle h, double* xdot);
