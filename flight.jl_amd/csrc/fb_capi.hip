@@ -22,6 +22,7 @@
 #include "poles_kernels.hpp"
 #include "timeresp_kernels.hpp"
 #include "connect_kernels.hpp"
+#include "dconnect_kernels.hpp"
 #include "surgery_kernels.hpp"
 #include "c2d_kernels.hpp"
 #include "dlqr_kernels.hpp"
@@ -231,6 +232,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 #include "fb_poles.inc"
 #include "fb_timeresp.inc"
 #include "fb_connect.inc"
+#include "fb_dconnect.inc"
 #include "fb_surgery.inc"
 #include "fb_c2d.inc"
 #include "fb_dlqr.inc"

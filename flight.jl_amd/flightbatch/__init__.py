@@ -33,3 +33,4 @@ from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult,
                      check_results)
 from . import dpid  # noqa: F401
 from .dpid import DPIDMetricsResult, build_dpid, dpid_metrics, optimize_dpid  # noqa: F401  (the sampled law on a sampled LinearWorld)
+from .dconnect import dconnect, dintegrator_world, dpid_world, dstate_feedback, dseries, dunity_feedback  # noqa: F401  (`dconnect` is the verb)

@@ -73,6 +73,7 @@ def _load():
         "fb_lss_dfreqresp": ([H, C.c_int32, C.c_int32, D, C.c_int32, D, D], C.c_int32),
         "fb_lss_dmargins": ([H, C.c_int32, C.c_int32, D, C.c_int32, D, D, I32, D, I32], C.c_int32),
         "fb_lss_dpoles": ([H, D, D, I32, I32], C.c_int32),
+        "fb_lss_dconnect": ([H, H, I32, C.c_int32, I32, C.c_int32, D, C.c_int32, D, C.c_int32, C.c_int32, I32, C.c_int32, I32, C.POINTER(H)], C.c_int32),
         "fb_lss_dpid_metrics": ([H, C.c_int32, C.c_int32, D, C.c_int32, C.c_double, D, D, D, C.c_int32, D, D, I32, I32], C.c_int32),
         "fb_f_step": ([H], C.c_int32),
         "fb_f_periodic": ([H], C.c_int32),

@@ -481,6 +481,22 @@ function dpoles(w::LinearWorld)
     check(ccall((:fb_lss_dpoles, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}), w.handle, re, im, iters, status))
     return (; re, im, iters, status)
 end
+"`connect` on sampled `LinearWorld`s with the same Ts, with unit delays (`fb_lss_dconnect`): `delays` are 1-based rows of z = [y_p; y_c] that are also
+kept one sample, q_k(t) = z[delays_k](t - 1); `reads` and `outputs` are 1-based rows of the extended vector [z; q] (`outputs = nothing`: every
+row), so a read or an output takes a signal now or one sample late. `feedback`, `inputs` and the status are `connect`'s. Returns the new sampled
+`LinearWorld` (states [x_p; x_c; q], inputs w, outputs [z; q][outputs], the plant's Ts, at rest) and status. A longer delay is a chain of calls."
+function dconnect(p::LinearWorld, c::Union{LinearWorld, Nothing} = nothing; feedback::Array{Float64}, inputs::Array{Float64}, reads, outputs = nothing,
+                  delays = Int[])
+    dz = Int32.(delays .- 1); jz = Int32.(reads .- 1); iz = outputs === nothing ? Int32[] : Int32.(outputs .- 1)
+    nw = size(inputs, ndims(inputs))
+    status = Vector{Int32}(undef, p.n)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:fb_lss_dconnect, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Int32,
+                                                Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                p.handle, c === nothing ? C_NULL : c.handle, isempty(dz) ? C_NULL : dz, length(dz), jz, length(jz), feedback,
+                ndims(feedback) == 3 ? 1 : 0, inputs, ndims(inputs) == 3 ? 1 : 0, nw, outputs === nothing ? C_NULL : iz, length(iz), status, h))
+    return (; world = LinearWorld(h[]), status)
+end
 "`optimize_PID`'s metrics under the sampled PID law (`f_periodic!` of `PID` every Ts: backward-Euler integrator and filtered derivative,
 output clamp, integrator halted while clamped) for every (system, candidate) pair of a sampled `LinearWorld`, channel (iu, iy) (1-based).
 `pid` is N x m x 4 (k_p, k_i, k_d, τ_f >= 0); `bounds` is `nothing` or N x m x 2 (lo, hi; either may be infinite; a finite bound needs d = 0);

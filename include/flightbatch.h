@@ -623,6 +623,32 @@ int32_t fb_lss_dmargins(fb_handle lss, int32_t iu, int32_t iy, const double* w, 
                         int32_t* status /* [N] */);
 int32_t fb_lss_dpoles(fb_handle lss, double* re, double* im, int32_t* iters, int32_t* status);
 
+/* ---- connect on SAMPLED Model(lss) batches, with unit delays (the `connect`, `series` and `feedback` calls of FA design/c172/c172x_design.jl
+ * on the loops FP/control.jl runs in f_periodic! every dt = 0.02; docs/design/linearize.md, "Closing sampled loops on the device") ------------
+ * fb_lss_connect's contract (above) for two SAMPLED FB_MODEL_LSS handles (fb_lss_c2d, fb_lss_dlqr's closed, fb_lss_set_sampled, an earlier
+ * fb_lss_dconnect) with the same Ts, bit for bit, with one element more: dz [nd] names rows of z = [y_p; y_c] that are also kept one sample,
+ * q_k(t) = z[dz_k](t - 1); a row may be named more than once, a longer delay is a chain of calls. In deviation coordinates (delta, x0, u0, y0
+ * play no part) the extended signal vector is ze = [y_p; y_c; q] (nz + nd rows), the extended state xe = [x_p; x_c; q] (nx' = nx_p + nx_c +
+ * nd rows), and with the stacked block-diagonal (A, B, C, D) of fb_lss_connect
+ *     Ae = [[A, 0], [C[dz], 0]],  Be = [B; D[dz]],  Ce = [[C, 0], [0, I]],  De = [D; 0]
+ *     v = F ze[jz] + G w,  outputs ze[iz]          jz and iz index the EXTENDED vector: a read or an output is a signal now or one sample late
+ *     E = inv(I - F De[jz, :]), M = E F Ce[jz, :], Nw = E G
+ *     Phi' = Ae + Be M,  Gamma' = Be Nw,  C' = Ce[iz, :] + De[iz, :] M,  D' = De[iz, :] Nw
+ * A delayed read adds nothing to I - F De[jz, :]: an interconnection that is ill-posed as a static one is well-posed when the signal
+ * arrives a sample late. F, G, their layouts, status [N] (FB_CONNECT_NOT_FINITE, FB_CONNECT_ILL_POSED; such a system gets NaN matrices, the
+ * call returns 0, no other system changes in any bit) are fb_lss_connect's. iz = NULL means every row of ze (nz + nd <= 64). With nd = 0 the
+ * four matrices have the bits fb_lss_connect gives on continuous handles that hold the same matrices.
+ * The new handle: an ordinary sampled FB_MODEL_LSS handle with p's Ts (dt = Ts, delta = 0), at x = 0, u = 0, t = 0, on p's device with p's
+ * stream rule; fb_step runs the map. p and c are only read. Refused, with nothing launched and no handle created: everything fb_lss_connect
+ * refuses for handles, sizes and NULL arguments (with nx' <= 32 and nz + nd <= FB_CONNECT_NZ_MAX in the places of nx and nz), a continuous
+ * plant or compensator ("a discrete-time verb on a continuous model"), a compensator whose Ts differs from the plant's in any bit, nd
+ * outside 0 .. FB_DCONNECT_ND_MAX, nd > 0 with a NULL dz, an entry of dz outside [0, nz), an entry of jz or iz outside [0, nz + nd).
+ * fb_lss_connect keeps refusing a sampled handle. */
+enum { FB_DCONNECT_ND_MAX = 31 };
+int32_t fb_lss_dconnect(fb_handle p, fb_handle c /* NULL: no compensator */, const int32_t* dz /* [nd] or NULL */, int32_t nd,
+                        const int32_t* jz, int32_t nf, const double* F, int32_t f_per_system, const double* G, int32_t g_per_system, int32_t nw,
+                        const int32_t* iz, int32_t ny, int32_t* status, fb_handle* out);
+
 /* ---- discrete PID design: the metrics of optimize_PID under the sampled law on a batch of sampled models (f_periodic! of PID,
  * FP/control.jl:431-471, the law Cessna172Xv2 and Robot2D run every dt = 0.02; FA design/pidopt.jl: Metrics :36-64, cost :66-70;
  * docs/design/linearize.md, "Discrete PID design on the device") ----------------------------------------------------------------------------
