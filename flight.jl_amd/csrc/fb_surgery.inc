@@ -6,6 +6,57 @@
 // fb_timing_begin_per_launch on the source stamps them); the new handle's copy of the model is then written by k_lss_gather through the
 // subsystem lists, like fb_lss_from_linearization's.
 
+// fb_lss_steady and fb_lss_dsteady (fb_dtracker.inc) behind their handle checks: the sizes, the lists, the blocks and the one kernel, whose
+// DISC instance subtracts the identity from Phi while it stages L. K_xi and K_fbk are the discrete verb's only.
+static int32_t steady_run(const char* verb, fb_handle h, bool disc, const int32_t* iz, int32_t nz, const double* K, const double* K_xi,
+                          int32_t k_per_system, double* X, double* U, double* K_fbk, double* K_fwd, double* rpiv, int32_t* status) {
+    const LssState* L = h->lss;
+    const int nx = L->nx, nu = L->nu, ny = L->ny;
+    if (nx + nu > FB_SURGERY_N_MAX) return fail("%s: nx + nu = %d exceeds FB_SURGERY_N_MAX = %d", verb, nx + nu, (int)FB_SURGERY_N_MAX);
+    if (nz != nu) return fail("%s: nz = %d, the map takes as many output rows as the model has inputs (nu = %d)", verb, (int)nz, nu);
+    if (!iz) return fail("%s: iz is required", verb);
+    if (!lists_in_range(verb, iz, nz, ny, "iz")) return -1;
+    if (K_fwd && !K) return fail("%s: K_fwd = U + K X needs K", verb);
+    if ((K_xi || K_fbk) && !K) return fail("%s: K_fbk = K - Ts K_xi C_z needs K", verb);
+
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t n = h->n;
+    const size_t un = (size_t)n, per = k_per_system ? un : 1;
+    const size_t szK = K ? (size_t)nu * nx * per : 0, szXi = K_xi ? (size_t)nu * nu * per : 0, szX = (size_t)nx * nu * un, szU = (size_t)nu * nu * un;
+    const size_t szF = K_fbk ? (size_t)nu * nx * un : 0;
+    DevBlocks blocks;
+    double* d = nullptr;
+    int32_t* di = nullptr;
+    if (int32_t rc = blocks.alloc(&d, szK + szXi + szX + 2 * szU + szF + un)) return rc;
+    if (int32_t rc = blocks.alloc(&di, (size_t)nz + un)) return rc;
+    fbm::SteadyArgs a = {};
+    verb_args(a, h);
+    double *dK = d, *dXi = dK + szK;
+    a.X = dXi + szXi; a.U = a.X + szX; a.Kfwd = K ? a.U + szU : nullptr; a.Kfbk = K_fbk ? a.U + 2 * szU : nullptr; a.rpiv = a.U + 2 * szU + szF;
+    a.iz = di; a.status = di + nz;
+    a.Ts = L->Ts;
+    HIPCHK(hipMemcpyAsync(di, iz, sizeof(int32_t) * nz, hipMemcpyHostToDevice, h->stream));
+    if (K) {
+        HIPCHK(hipMemcpyAsync(dK, K, sizeof(double) * szK, hipMemcpyHostToDevice, h->stream));
+        a.K = dK; a.k_e = k_per_system ? n : 1; a.k_s = k_per_system ? 1 : 0;
+    }
+    if (K_xi) {
+        HIPCHK(hipMemcpyAsync(dXi, K_xi, sizeof(double) * szXi, hipMemcpyHostToDevice, h->stream));
+        a.Kxi = dXi;
+    }
+    if (disc) {
+        if (int32_t rc = family_launch(h, group_for(nx + nu), n, a, [](auto P) { return fbj::k_dsteady<P.value>; })) return rc;
+    } else if (int32_t rc = family_launch(h, group_for(nx + nu), n, a, [](auto P) { return fbm::k_steady<P.value>; })) return rc;
+    if (X) HIPCHK(hipMemcpyAsync(X, a.X, sizeof(double) * szX, hipMemcpyDeviceToHost, h->stream));
+    if (U) HIPCHK(hipMemcpyAsync(U, a.U, sizeof(double) * szU, hipMemcpyDeviceToHost, h->stream));
+    if (K_fbk) HIPCHK(hipMemcpyAsync(K_fbk, a.Kfbk, sizeof(double) * szF, hipMemcpyDeviceToHost, h->stream));
+    if (K_fwd) HIPCHK(hipMemcpyAsync(K_fwd, a.Kfwd, sizeof(double) * szU, hipMemcpyDeviceToHost, h->stream));
+    if (rpiv) HIPCHK(hipMemcpyAsync(rpiv, a.rpiv, sizeof(double) * un, hipMemcpyDeviceToHost, h->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 extern "C" {
 
 int32_t fb_lss_transform(fb_handle src, const int32_t* rows, const int32_t* xdot_zero, const int32_t* ix, int32_t nxo, const int32_t* iu, int32_t nuo,
@@ -62,41 +113,7 @@ int32_t fb_lss_steady(fb_handle h, const int32_t* iz, int32_t nz, const double* 
     if (int32_t rc = verb_handle(verb, h, FB_SURGERY_N_MAX - 1, "steady-state map", "nx + nu <= FB_SURGERY_N_MAX")) return rc;
     if (int32_t rc = verb_model(verb, h)) return rc;
     if (int32_t rc = verb_continuous(verb, h)) return rc;
-    const LssState* L = h->lss;
-    const int nx = L->nx, nu = L->nu, ny = L->ny;
-    if (nx + nu > FB_SURGERY_N_MAX) return fail("fb_lss_steady: nx + nu = %d exceeds FB_SURGERY_N_MAX = %d", nx + nu, (int)FB_SURGERY_N_MAX);
-    if (nz != nu) return fail("fb_lss_steady: nz = %d, the map takes as many output rows as the model has inputs (nu = %d)", (int)nz, nu);
-    if (!iz) return fail("fb_lss_steady: iz is required");
-    if (!lists_in_range(verb, iz, nz, ny, "iz")) return -1;
-    if (K_fwd && !K) return fail("fb_lss_steady: K_fwd = U + K X needs K");
-
-    HIPCHK(hipSetDevice(h->device));
-    const int64_t n = h->n;
-    const size_t un = (size_t)n;
-    const size_t szK = K ? (size_t)nu * nx * (k_per_system ? un : 1) : 0, szX = (size_t)nx * nu * un, szU = (size_t)nu * nu * un;
-    DevBlocks blocks;
-    double* d = nullptr;
-    int32_t* di = nullptr;
-    if (int32_t rc = blocks.alloc(&d, szK + szX + 2 * szU + un)) return rc;
-    if (int32_t rc = blocks.alloc(&di, (size_t)nz + un)) return rc;
-    fbm::SteadyArgs a = {};
-    verb_args(a, h);
-    double* dK = d;
-    a.X = dK + szK; a.U = a.X + szX; a.Kfwd = K ? a.U + szU : nullptr; a.rpiv = a.U + 2 * szU;
-    a.iz = di; a.status = di + nz;
-    HIPCHK(hipMemcpyAsync(di, iz, sizeof(int32_t) * nz, hipMemcpyHostToDevice, h->stream));
-    if (K) {
-        HIPCHK(hipMemcpyAsync(dK, K, sizeof(double) * szK, hipMemcpyHostToDevice, h->stream));
-        a.K = dK; a.k_e = k_per_system ? n : 1; a.k_s = k_per_system ? 1 : 0;
-    }
-    if (int32_t rc = family_launch(h, group_for(nx + nu), n, a, [](auto P) { return fbm::k_steady<P.value>; })) return rc;
-    if (X) HIPCHK(hipMemcpyAsync(X, a.X, sizeof(double) * szX, hipMemcpyDeviceToHost, h->stream));
-    if (U) HIPCHK(hipMemcpyAsync(U, a.U, sizeof(double) * szU, hipMemcpyDeviceToHost, h->stream));
-    if (K_fwd) HIPCHK(hipMemcpyAsync(K_fwd, a.Kfwd, sizeof(double) * szU, hipMemcpyDeviceToHost, h->stream));
-    if (rpiv) HIPCHK(hipMemcpyAsync(rpiv, a.rpiv, sizeof(double) * un, hipMemcpyDeviceToHost, h->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, a.status, sizeof(int32_t) * un, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return steady_run(verb, h, false, iz, nz, K, nullptr, k_per_system, X, U, nullptr, K_fwd, rpiv, status);
 }
 
 }  // extern "C"

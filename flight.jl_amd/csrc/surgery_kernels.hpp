@@ -4,6 +4,8 @@
 // M = inv([A B; C D]) (:184-188, :371-381).
 //   k_transform  T = C[rows, :];  A' = T A inv(T), B' = T B, C' = C inv(T), D' = D, xdot0' = T xdot0 (masked entries exactly 0), x0' = y0[rows]
 //   k_steady     L = [A B; C[iz, :] D[iz, :]];  L [X; U] = [0; I];  K_fwd = U + K X
+//                DISC (fb_lss_dsteady, a sampled model): L = [Phi - I, Gamma; C_z D_z], the identity subtracted while the rows are staged;
+//                K_fbk = K - Ts K_xi C_z (K_xi given), K_fwd = U + K_fbk X
 // One system per group of P lanes of one wave (P = 8, 16 or 32, the smallest with a lane per row of T or of L; 64 / P systems per wave,
 // one wave per workgroup). Lane r owns row r of the augmented rows ([T | I], [L | 0; I]) as an fbg::Row; the family's solve
 // (fbg::gj_solve, lss_group.hpp: Gauss-Jordan elimination, the rows staying with their lanes) puts row k of the solution
@@ -43,6 +45,10 @@ struct SteadyArgs {
     int64_t k_e, k_s;
     double *X, *U, *Kfwd;                 // [(r + nx c) n + i], [(r + nu c) n + i] twice; each may be NULL
     int32_t* status; double* rpiv;
+    // DISC only: K_xi [nu x nu] by K's rule (may be NULL), the sample time, K_fbk [(r + nu c) n + i] over nx columns (may be NULL)
+    const double* Kxi;
+    double Ts;
+    double* Kfbk;
 };
 
 template <int P>
@@ -178,8 +184,9 @@ __global__ __launch_bounds__(SG_WAVE) void k_transform(TransformArgs a) {
     }
 }
 
-template <int P>
-__global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
+// the body of k_steady (DISC = false) and of fbj::k_dsteady (DISC = true, dtracker_kernels.hpp): one statement of the map for both times
+template <int P, bool DISC>
+__device__ __forceinline__ void steady_body(const SteadyArgs& a) {
     constexpr int NW = SG_NU_MAX, LD = NW + 1, NG = SG_WAVE / P, ROW = P + NW, GRP = ROW + P * LD;   // (ROW and GRP are even: 16-byte rows)
     __shared__ __attribute__((aligned(16))) double lds[NG * GRP];
     const fbg::Lanes<P> g;
@@ -205,18 +212,33 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
         double e = 0.0;
         if (live && c < m) e = src[(int64_t)((top && c >= nx) ? a.G + c - nx : c) * pitch];
         fin = fin && is_fin(e);
+        if constexpr (DISC) { if (top && c == r) e -= 1.0; }
         lr.e[c] = e;
     }
 #pragma unroll
     for (int c = 0; c < NW; c++) lr.rhs[c] = (live && r == nx + c) ? 1.0 : 0.0;
     if (a.K && r < nu)
         for (int k = 0; k < nx; k++) fin = fin && is_fin(a.K[((int64_t)r + (int64_t)nu * k) * a.k_e + i * a.k_s]);
+    // DISC with K_xi: its entries, and whether D_z has a non-zero entry (the lanes of the rows of [C_z | D_z] look at their own)
+    bool direct = false;
+    if constexpr (DISC) {
+        if (a.Kxi) {
+            if (r < nu)
+                for (int k = 0; k < nu; k++) fin = fin && is_fin(a.Kxi[((int64_t)r + (int64_t)nu * k) * a.k_e + i * a.k_s]);
+            bool dnz = false;
+#pragma unroll
+            for (int c = 0; c < P; c++) dnz = dnz || (live && !top && c >= nx && lr.e[c] != 0.0);
+            direct = g.any(dnz);
+        }
+    }
 
     // ---- [. | X; U]: row k of [X; U] at row k of sol
     const Solve sv = gj_solve<P, LD>(g, lr, prow, sol, live, m);
 
-    const Verdict vd = verdict<P>(g, fin, sv, FB_SURGERY_NOT_FINITE, FB_SURGERY_SINGULAR);
+    Verdict vd = verdict<P>(g, fin, sv, FB_SURGERY_NOT_FINITE, FB_SURGERY_SINGULAR);
     const bool good = vd.status == 0;
+    if (good && direct) vd.status = FB_DSTEADY_DIRECT;   // (X and U are delivered; K_fbk and K_fwd are not)
+    const bool gains = vd.status == 0;
     const double nan = __builtin_nan("");
     if (valid && r == 0) {
         if (a.status) a.status[i] = vd.status;
@@ -233,23 +255,35 @@ __global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) {
                 if (c < nu) out[staged_index(n, i, rows, ro, c)] = good ? sol[r * LD + c] : nan;
         }
     }
-    // ---- row r of K_fwd = U + K X
-    if (a.K && a.Kfwd && r < nu) {
+    // ---- row r of K_fwd = U + K X (DISC: of K_fbk = K - Ts K_xi C_z, and K_fwd = U + K_fbk X)
+    if (a.K && (a.Kfwd || (DISC && a.Kfbk)) && r < nu) {
         double acc[NW];
 #pragma unroll
         for (int c = 0; c < NW; c++) acc[c] = sol[(nx + r) * LD + c];
         for (int k = 0; k < nx; k++) {
-            const double kk = a.K[((int64_t)r + (int64_t)nu * k) * a.k_e + i * a.k_s];
+            double kk = a.K[((int64_t)r + (int64_t)nu * k) * a.k_e + i * a.k_s];
+            if constexpr (DISC) {
+                if (a.Kxi) {
+                    double s = 0.0;
+                    for (int c = 0; c < nu; c++)
+                        s = fma(a.Kxi[((int64_t)r + (int64_t)nu * c) * a.k_e + i * a.k_s], a.cd[cd_index(n, i, ny, a.iz[c], k)], s);
+                    kk = fma(-a.Ts, s, kk);
+                }
+                if (a.Kfbk && valid) a.Kfbk[staged_index(n, i, nu, r, k)] = gains ? kk : nan;
+            }
             const double* q = sol + k * LD;
 #pragma unroll
             for (int c = 0; c < NW; c++) acc[c] = fma(kk, q[c], acc[c]);
         }
-        if (valid) {
+        if (valid && a.Kfwd) {
 #pragma unroll
             for (int c = 0; c < NW; c++)
-                if (c < nu) a.Kfwd[staged_index(n, i, nu, r, c)] = good ? acc[c] : nan;
+                if (c < nu) a.Kfwd[staged_index(n, i, nu, r, c)] = gains ? acc[c] : nan;
         }
     }
 }
+
+template <int P>
+__global__ __launch_bounds__(SG_WAVE) void k_steady(SteadyArgs a) { steady_body<P, false>(a); }
 
 }  // namespace fbm

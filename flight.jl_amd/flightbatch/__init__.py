@@ -34,3 +34,6 @@ from .pidopt import (PIDData, Metrics, Settings, PIDMetricsResult, PIDOptResult,
 from . import dpid  # noqa: F401
 from .dpid import DPIDMetricsResult, build_dpid, dpid_metrics, optimize_dpid  # noqa: F401  (the sampled law on a sampled LinearWorld)
 from .dconnect import dconnect, dintegrator_world, dpid_world, dstate_feedback, dseries, dunity_feedback  # noqa: F401  (`dconnect` is the verb)
+from . import dtracker  # noqa: F401
+from .dtracker import (DSteadyResult, DTrackerResult, dsteady_state, dtracker_metrics, dintegrators_world, dintegral_augmentation,  # noqa: F401
+                       dlqr_tracker, dtracker_world)

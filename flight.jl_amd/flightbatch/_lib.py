@@ -75,6 +75,8 @@ def _load():
         "fb_lss_dpoles": ([H, D, D, I32, I32], C.c_int32),
         "fb_lss_dconnect": ([H, H, I32, C.c_int32, I32, C.c_int32, D, C.c_int32, D, C.c_int32, C.c_int32, I32, C.c_int32, I32, C.POINTER(H)], C.c_int32),
         "fb_lss_dpid_metrics": ([H, C.c_int32, C.c_int32, D, C.c_int32, C.c_double, D, D, D, C.c_int32, D, D, I32, I32], C.c_int32),
+        "fb_lss_dtracker_metrics": ([H, I32, C.c_int32, D, D, D, D, C.c_int32, D, C.c_double, C.c_int32, D, D, I32, D, D, I32], C.c_int32),
+        "fb_lss_dsteady": ([H, I32, C.c_int32, D, D, C.c_int32, D, D, D, D, D, I32], C.c_int32),
         "fb_f_step": ([H], C.c_int32),
         "fb_f_periodic": ([H], C.c_int32),
         "fb_get_outputs": ([H, D], C.c_int32),

@@ -515,6 +515,45 @@ function dpid_metrics(w::LinearWorld, iu::Integer, iy::Integer, freqs::Vector{Fl
                 bounds === nothing ? C_NULL : bounds, m, metrics, cost, counts, status))
     return (; metrics, cost, status, counts)
 end
+"The sampled LQR tracker law (`f_periodic!` of `LQR`, FP/control.jl:708-743) on every (system, candidate) pair of a sampled `LinearWorld`:
+the step response to `zref` (nz numbers, the batch's) of the command variables `z` (1-based output rows) from rest over round(t_sim / Ts)
+ticks. Gains: `k_fbk` N x m x nu x nx, `k_fwd` and `k_int` N x m x nu x nz; `bounds` N x m x nu x 2 (lo, hi on the deviation of u) or nothing.
+Returns zmet N x m x nz x 3 (ie, ef, zp), umet N x m x nu x 2 (iu, up), counts N x m x nu x 2 (clamped, halted ticks), the samples
+zs N x m x nz x ns and us N x m x nu x ns (every `stride`-th and the last) and status N x m (0, FB_DTRACK_DIVERGED = 1, FB_DTRACK_NOT_FINITE = 2)."
+function dtracker_metrics(w::LinearWorld, z, k_fbk::Array{Float64, 4}, k_fwd::Array{Float64, 4}, k_int::Array{Float64, 4}, zref::Vector{Float64},
+                          t_sim::Real; bounds::Union{Array{Float64, 4}, Nothing} = nothing, stride::Integer = 1)
+    iz = Int32.(z .- 1)
+    nz = length(iz); m = size(k_fbk, 2)
+    size(k_fbk) == (w.n, m, w.nu, w.nx) || throw(DimensionMismatch("k_fbk must be N x m x nu x nx"))
+    size(k_fwd) == (w.n, m, w.nu, nz) && size(k_int) == (w.n, m, w.nu, nz) || throw(DimensionMismatch("k_fwd and k_int must be N x m x nu x nz"))
+    bounds === nothing || size(bounds) == (w.n, m, w.nu, 2) || throw(DimensionMismatch("bounds must be N x m x nu x 2"))
+    length(zref) == nz || throw(DimensionMismatch("zref must have nz entries"))
+    nt = round(Int, t_sim / sample_time(w))
+    ns = Int(ccall((:fb_lss_stepinfo_samples, lib), Cint, (Cint, Cint), nt, stride))
+    ns > 0 || throw(DimensionMismatch("t_sim / Ts and stride must both be at least 1"))
+    zmet = Array{Float64}(undef, w.n, m, nz, 3); umet = Array{Float64}(undef, w.n, m, w.nu, 2); counts = Array{Int32}(undef, w.n, m, w.nu, 2)
+    zs = Array{Float64}(undef, w.n, m, nz, ns); us = Array{Float64}(undef, w.n, m, w.nu, ns); status = Matrix{Int32}(undef, w.n, m)
+    check(ccall((:fb_lss_dtracker_metrics, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                                                        Ptr{Cdouble}, Cdouble, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iz, nz, k_fbk, k_fwd, k_int, bounds === nothing ? C_NULL : bounds, m, zref, t_sim, stride, zmet, umet, counts, zs, us, status))
+    return (; zmet, umet, counts, zs, us, status)
+end
+"`steady_state` for a sampled `LinearWorld`: [X; U] = the last nz columns of inv([Phi - I, Gamma; C[z, :], D[z, :]]), k_fbk = k - Ts k_xi C_z
+(k_xi given; else k) and k_fwd = U + k_fbk X. k (nu x nx) and k_xi (nu x nz): both for the batch, or both N x nu x . per system. status: 0,
+FB_SURGERY_SINGULAR = 1, FB_SURGERY_NOT_FINITE = 2, FB_DSTEADY_DIRECT = 4 (k_xi on a system with D_z != 0: k_fbk and k_fwd NaN)."
+function dsteady_state(w::LinearWorld, z; k::Union{Array{Float64}, Nothing} = nothing, k_xi::Union{Array{Float64}, Nothing} = nothing)
+    iz = Int32.(z .- 1)
+    nz = length(iz)
+    x = Array{Float64}(undef, w.n, w.nx, nz); u = Array{Float64}(undef, w.n, w.nu, nz)
+    k_fbk = k === nothing ? nothing : Array{Float64}(undef, w.n, w.nu, w.nx)
+    k_fwd = k === nothing ? nothing : Array{Float64}(undef, w.n, w.nu, nz)
+    status = Vector{Int32}(undef, w.n); rpiv = Vector{Float64}(undef, w.n)
+    check(ccall((:fb_lss_dsteady, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                               Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}),
+                w.handle, iz, nz, k === nothing ? C_NULL : k, k_xi === nothing ? C_NULL : k_xi, k !== nothing && ndims(k) == 3 ? 1 : 0, x, u,
+                k === nothing ? C_NULL : k_fbk, k === nothing ? C_NULL : k_fwd, rpiv, status))
+    return (; x, u, k_fbk, k_fwd, status, rpiv)
+end
 "`:panel` or `:shfl`: how the stepper's lanes exchange stage values (FLIGHTBATCH_LSS_EXCHANGE when the handle was created)"
 function exchange(w::LinearWorld)
     xch = Ref{Int32}(-1)

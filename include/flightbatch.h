@@ -522,7 +522,8 @@ int32_t fb_lss_steady(fb_handle lss, const int32_t* iz, int32_t nz, const double
  * from Ts in any bit); fb_f_ode(NULL) refreshes y, fb_f_ode(xdot) is refused (no derivative); fb_lss_get_model returns Phi and Gamma;
  * fb_lss_get_cd is unchanged; fb_lss_stepinfo samples the map at t_k = k Ts (dt must be Ts bit for bit; 0 or a non-finite dt means Ts);
  * fb_lss_set_model, fb_lss_c2d, fb_lqr, fb_pid_metrics, fb_lss_freqresp, fb_lss_poles, fb_lss_connect (either argument),
- * fb_lss_transform and fb_lss_steady are refused ("a continuous-time verb on a sampled model"); fb_lss_dlqr (below) designs on it. */
+ * fb_lss_transform and fb_lss_steady are refused ("a continuous-time verb on a sampled model"); fb_lss_dlqr (below) designs on it, and
+ * fb_lss_dsteady (below) is the steady-state map of a sampled model. */
 enum { FB_C2D_NOT_FINITE = 1, FB_C2D_RANGE = 2, FB_C2D_SQUARINGS_MAX = 30 };
 int32_t fb_lss_c2d(fb_handle lss, double Ts, int32_t* squarings /* [N] or NULL */, int32_t* status /* [N] or NULL */, fb_handle* out);
 int32_t fb_lss_sample_time(fb_handle h, double* Ts);   /* 0 for a continuous LinearizedSS handle */
@@ -685,6 +686,51 @@ enum { FB_DPID_DIVERGED = 1, FB_DPID_SINGULAR = 2, FB_DPID_DIRECT = 4, FB_DPID_N
 int32_t fb_lss_dpid_metrics(fb_handle lss, int32_t iu, int32_t iy, const double* w, int32_t nw, double t_sim, const double* weights,
                             const double* pid, const double* bounds /* [2 x m x N] or NULL */, int32_t m, double* metrics, double* cost,
                             int32_t* counts /* [2 x m x N] or NULL */, int32_t* status);
+
+/* ---- discrete LQR trackers: the sampled tracker law on a batch of sampled models (f_periodic! of LQR, FP/control.jl:708-743, the law
+ * Cessna172Xv2's te2te, tv2te, vh2te, ar2ar and phibeta2ar and Robot2D's tracker run every dt = 0.02; FA design/c172/c172x_design.jl designs
+ * their gains in continuous time; docs/design/linearize.md, "Discrete LQR trackers on the device") --------------------------------------------
+ * fb_lss_dtracker_metrics. The plant is each system of a SAMPLED FB_MODEL_LSS handle with a model, in deviation coordinates: Phi, Gamma,
+ * C_z = C[iz, :], D_z = D[iz, :] (delta, x0, u0, y0 play no part). iz [nz] names output rows; 1 <= nu <= 8, 1 <= nz <= 8,
+ * nx + nu + nz <= FB_DTRACK_ROWS_MAX. A pair (system i, candidate j), 1 <= m <= 64 candidates per system, has K_fbk [nu x nx], K_fwd [nu x nz]
+ * and K_int [nu x nz], host arrays with element (r, c) of pair (i, j) at [((r + rows c) m + j) N + i]. bounds: NULL (no bounds) or
+ * [2 x nu x m x N], lo then hi, input r of pair (i, j) at [((s nu + r) m + j) N + i], lo < hi, either may be infinite; they bound the
+ * deviation. zref [nz]: the reference step, a host array, one for the batch, finite.
+ * From rest, ticks k = 0 .. N_t, N_t = round(t_sim / Ts), 1 <= N_t <= 200000, x_0 = 0, iota_-1 = 0, sat_-1 = 0, u_-1 = 0:
+ *     z_k = C_z x_k + D_z u_k-1        (the law samples its command variables before it writes its output: a fed-through command is last tick's)
+ *     e_k = zref - z_k;  v_k = K_int e_k;  halted_kj = v_kj sat_k-1,j > 0
+ *     iota_kj = iota_k-1,j when halted, else iota_k-1,j + Ts v_kj
+ *     free_k = iota_k + K_fwd zref - K_fbk x_k;  sat_k = (free_k >= hi) - (free_k <= lo);  u_k = clamp(free_k, lo, hi)
+ *     x_k+1 = Phi x_k + Gamma u_k
+ * (a rectangular integrator that includes the current sample, an output clamp per input, an integrator that halts, per input, while its
+ * output is clamped and its input pushes further into the bound; the reference block's sat_ext is 0.) Bounds of -Inf and +Inf give the
+ * bits of no bounds.
+ * Outputs, each may be NULL except status. zmet [3 x nz x m x N], per command variable c at [((k nz + c) m + j) N + i]: ie, the trapezoid
+ * mean of |e_c,k| over k = 0 .. N_t (fb_lss_dpid_metrics' rule); ef = |e_c,N_t|; zp = max_k |z_c,k|. umet [2 x nu x m x N], per input: iu, the
+ * trapezoid mean of |u_j,k|; up = max_k |u_j,k|. counts [2 x nu x m x N], per input: the ticks with sat != 0, then the ticks with the
+ * integrator halted. zs [ns x nz x m x N] and us [ns x nu x m x N]: every stride-th sample and the last one, ns =
+ * fb_lss_stepinfo_samples(N_t, stride), sample s stride at row s, sample N_t at row ns - 1. status [m x N]: 0; FB_DTRACK_DIVERGED: a sample
+ * of z or u was not finite or beyond 1e12 (the metrics are +Inf, the counts 0); FB_DTRACK_NOT_FINITE: a non-finite entry of Phi, Gamma, C_z,
+ * D_z or of the pair's gains (the metrics are NaN, the counts 0). The samples of a flagged pair are what the arithmetic gave. The call
+ * returns 0 in both cases and no other pair changes in any bit. Reads the handle's copy of the model, runs on its stream and changes
+ * nothing on the handle. Refused, with nothing launched: a NULL or non-LSS handle, a handle without a model, a continuous handle ("a
+ * discrete-time verb on a continuous model"), the size limits above, an entry of iz outside [0, ny), m outside 1 .. 64, t_sim not finite
+ * or N_t outside 1 .. 200000, stride < 1, lo >= hi or a NaN bound, a non-finite zref, a NULL iz, gain array, zref or status.
+ * fb_lss_dsteady: fb_lss_steady's contract (above) for a SAMPLED handle, with the discrete equilibrium: L_d = [Phi - I, Gamma; C_z, D_z],
+ *     L_d [X; U] = [0; I],  K_fbk = K - Ts K_xi C_z  (K_xi given; else K_fbk = K),  K_fwd = U + K_fbk X
+ * by the same elimination and pivot rule (the identity is subtracted while the rows are staged). K_xi [nu x nz] (may be NULL): a host array
+ * under K's batch or per-system rule; with it K is the state block and K_xi the integrator block of a gain designed on the augmentation
+ * [x_k; xi_k-1], xi_k = xi_k-1 + Ts z_k, and K_fbk, K_int = K_xi are the gains of the law above, whose integrator holds the current sample.
+ * K_fbk [nu x nx] comes home in fb_linearize's layout and may be NULL; K_xi and K_fbk need K. status: FB_SURGERY_SINGULAR and
+ * FB_SURGERY_NOT_FINITE as for fb_lss_steady (NOT_FINITE: an entry of L_d, K or K_xi); FB_DSTEADY_DIRECT: K_xi is given and D_z of that
+ * system has a non-zero entry (K_fbk and K_fwd are NaN; X and U are still delivered). Refused: what fb_lss_steady refuses, and a continuous
+ * handle ("a discrete-time verb on a continuous model"). fb_lss_steady keeps refusing a sampled one. */
+enum { FB_DTRACK_DIVERGED = 1, FB_DTRACK_NOT_FINITE = 2, FB_DTRACK_ROWS_MAX = 32, FB_DSTEADY_DIRECT = 4 };
+int32_t fb_lss_dtracker_metrics(fb_handle lss, const int32_t* iz, int32_t nz, const double* K_fbk, const double* K_fwd, const double* K_int,
+                                const double* bounds /* [2 x nu x m x N] or NULL */, int32_t m, const double* zref /* [nz] */, double t_sim,
+                                int32_t stride, double* zmet, double* umet, int32_t* counts, double* zs, double* us, int32_t* status);
+int32_t fb_lss_dsteady(fb_handle lss, const int32_t* iz, int32_t nz, const double* K, const double* K_xi /* or NULL */, int32_t k_per_system,
+                       double* X, double* U, double* K_fbk, double* K_fwd, double* rpiv, int32_t* status);
 
 /* f_ode!(world) : FP/world.jl:26-32. Uses current x, u, s; writes xdot [N x FB_NX] (may be NULL)
  * and refreshes the output record y. */
