@@ -86,8 +86,10 @@ static_assert(KC<KC_HALF_PI>::v == PI / 2 && KC<KC_GEOID_PER_RAD>::v == 1440 / (
 
 // fp64 square roots without the library's range scaling and special-case fix-up (9 instructions instead of 17; at one wave per
 // SIMD every instruction costs an issue slot): v_rsq_f64 seed, one coupled Goldschmidt step on (g ~ sqrt x, h ~ 1/(2 sqrt x))
-// and one residual correction -> <= 1 ulp. Arguments here are sums of squares and physical magnitudes: 0 and NaN behave as in
-// sqrt() (0 -> 0, NaN -> NaN); numbers below 1e-290 are treated as 0.
+// and one residual correction -> <= 1 ulp (measured: 0.50 ulp on the host whatever the seed's error up to 2^-23; the device's figure
+// is in docs/design/k_step_air.md, "Math primitives, measured", like every figure below). Arguments here are sums of squares and
+// physical magnitudes. DOMAIN [1e-280, 1e300]; 0 and NaN behave as in sqrt() (0 -> 0, NaN -> NaN); numbers below 1e-290 are treated
+// as 0 (the result is some number below 1e-145); +inf gives NaN (the seed is 0), unlike sqrt().
 template <class KP = KLit>
 FBD real sqrt(real x, const KP& K = KP{}) {
     if constexpr (sizeof(real) == 8) {
@@ -100,7 +102,8 @@ FBD real sqrt(real x, const KP& K = KP{}) {
         return ::sqrtf(x);
     }
 }
-FBD real rsqrt(real x) {   // x > 0
+// <= 1 ulp: 0.74 ulp on the host with a correctly rounded seed, 1.00 with any other (seed error up to 2^-23). x = 0 and x = +inf give NaN.
+FBD real rsqrt(real x) {   // x > 0, finite: [1e-280, 1e300] is tested
     if constexpr (sizeof(real) == 8) {
         double y = __builtin_amdgcn_rsq((double)x);
         double r = __builtin_fma(-0.5 * y, x * y, 0.5);
@@ -178,6 +181,8 @@ constexpr int LDS_RK_DOUBLES = LDS_RK_KNOTS + 40;
 // cos and sin of atan2(y, x) / 2 without evaluating the angle: half-angle identities arranged so that the
 // square root is always taken of a number >= 1/2 (no cancellation). Used for the z- and y-rotation quaternions
 // of the local-level frames, where only cos(angle/2), sin(angle/2) are needed (attitude.jl:288-308).
+// Two rsqrt deep: <= 3.36 ulp on either output (host, seed error up to 2^-23; 2.92 with a correctly rounded seed). DOMAIN: x^2 + y^2
+// neither overflows nor underflows, or x = y = 0. A NaN argument fails r2 > 0 and returns (1, 0) like (0, 0); an infinite one gives NaN.
 FBD void half_angle_cs(real y, real x, real& c, real& s) {
     // branch-free: with cx = x/r, sy = y/r and h = (1 + |cx|)/2 >= 1/2, t = sqrt h is the larger of |cos|, |sin| of the half angle and
     // w = |sy| / (2 t) the smaller; which is which depends on the sign of x. One rsqrt gives both t = h rs and 1/t = rs.
@@ -196,14 +201,25 @@ FBD void half_angle_cs(real y, real x, real& c, real& s) {
 // atan2 with one division: the octant's quotient t = min/max in [0, 1] is located on a 1/32 grid from a single-precision estimate,
 // atan t = atan t_i + atan r with r = (min - t_i max) / (max + t_i min), |r| <= 1/64, so that four series terms reach 1e-19; atan t_i
 // comes from a 33-entry table in LDS (tab). 53 instructions against the library's 70 (whose own polynomial needs 20 constants,
-// two s_mov each); error <= 1.6 ulp. atan2(0, 0) = 0; the sign of a zero x is not examined (atan2(0, -0) = 0, not π).
+// two s_mov each). Error: 2.07 ulp on the host with a correctly rounded division (worst where the quotient changes table entry just
+// below a power of two, y/x ~ 1/64; "<= 1.6" stood here unmeasured), <= 2.57 ulp with the device's 1-ulp division.
+// atan2(0, 0) = 0; the sign of a zero x is not examined (atan2(0, -0) = 0, not π).
+// DOMAIN: 1e-30 <= max(|x|, |y|) <= 1e30, or x = y = 0: the estimate is formed in single precision, and outside fp32's normal range it
+// is NaN or infinite — (1e-300, 1e-300) and (1e300, 1e300) select entry 0 and return 0.8349, not π/4; at fp32-denormal magnitudes
+// (1e-40, 1e-40) the estimate is NaN or infinite depending on how the denormals are treated, and the entry is 0 or (the index is
+// clamped) 32: the result is WRONG BUT BOUNDED there, an angle of the right sign within [0, π], and every read stays inside the table.
+// The call sites and their ranges are listed in docs/design/k_step_air.md: every one stays inside the domain for any state the
+// integrator can reach; a state SET with two components both in (0, 1e-30) next to a guard that looks at a third does not.
+// NaN does NOT come through: fmax / fmin drop it (atan2_tab(NaN, 1) = π/4, atan2_tab(NaN, NaN) = 0), so no caller may rely on this
+// function to carry a NaN state forward (none does: the norms and sums next to every call carry it). An infinite argument gives NaN.
 // XPOS: the caller guarantees x >= 0 and (x, y) != (0, 0) (x is a norm next to a non-zero y, or the cosine of a latitude): the
 // x < 0 reflection and the atan2(0, 0) guard drop out.
 template <bool XPOS = false, class KP = KLit>
 FBD double atan2_tab(double y, double x, lds_cptr tab, const KP& K = KP{}) {
     const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
     const double mx = __builtin_fmax(ax, ay), mn = __builtin_fmin(ax, ay);
-    const int i = (int)__builtin_rintf(((float)mn * __builtin_amdgcn_rcpf((float)mx)) * 32.0f);   // (NaN -> 0)
+    const int i0 = (int)__builtin_rintf(((float)mn * __builtin_amdgcn_rcpf((float)mx)) * 32.0f);   // (NaN -> 0; never negative)
+    const int i = i0 < ATAN_N - 1 ? i0 : ATAN_N - 1;   // in the domain i0 <= 32 already; outside it (an infinite estimate) the read stays in the table
     const double ti = (double)i * (1.0 / 32);
     const double r = (mn - ti * mx) / (mx + ti * mn), s = r * r;
     double p = __builtin_fma(s, (double)kc<KC_AT_C9>(K), (double)kc<KC_AT_C7>(K));
@@ -218,7 +234,10 @@ FBD double atan2_tab(double y, double x, lds_cptr tab, const KP& K = KP{}) {
     return __builtin_copysign(a, y);
 }
 // single-precision atan2 for the fp32 stepper: t = min/max through v_rcp_f32, atan t = t P(t^2) with a degree-7 near-minimax P
-// (coefficients as VOP2 literals: one instruction per term), 2e-7 absolute; 25 instructions against the library's ~55
+// (coefficients as VOP2 literals: one instruction per term); 25 instructions against the library's ~55. Absolute error: the polynomial
+// 1.09e-7, with v_rcp_f32 and the roundings <= 3.0e-7 in the first octant, <= 4.1e-7 after π/2 - a (XPOS), <= 6.1e-7 after π - a, where
+// one ulp of the result is 2.4e-7 (the count: tests/math_cases.py, ATAN2_FAST_BOUND; "2e-7 absolute" stood here: the host measures
+// 3.5e-7 near ±π with a correctly rounded reciprocal). DOMAIN and NaN as atan2_tab: max(|x|, |y|) in [1e-30, 1e30] or both zero.
 template <bool XPOS = false>
 FBD float atan2_fast(float y, float x) {
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
@@ -238,7 +257,9 @@ FBD float atan2_fast(float y, float x) {
     return __builtin_copysignf(a, y);
 }
 // exp / log of the stepping kernels' fast path. fp64: the library's; fp32: v_exp_f32 / v_log_f32 on the base-2 forms (1 ulp of
-// the hardware functions, 3 instructions instead of ~15: the fp32 stepper is VALU-issue-bound, every instruction counts)
+// the hardware functions, 3 instructions instead of ~15: the fp32 stepper is VALU-issue-bound, every instruction counts). Absolute error
+// on the ISA's arguments, from that 1 ulp, the fp32 constant and the product's rounding: exp_step <= 2.6e-7 on [-2, 0.2], log_step
+// <= 5.8e-8 on [0.69, 1.03] (tests/math_cases.py, EXP_STEP_BOUND / LOG_STEP_BOUND).
 FBD real exp_step(real x) {
     if constexpr (sizeof(real) == 8) return exp(x); else return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
 }
@@ -250,7 +271,9 @@ FBD real atan2_step(real y, real x, lds_cptr tab, const KP& K = KP{}) {   // the
     if constexpr (sizeof(real) == 8) return atan2_tab<XPOS>(y, x, tab, K); else return atan2_fast<XPOS>(y, x);
 }
 // log u for u near 1 (the troposphere's temperature ratio, 0.7 .. 1.1): 2 atanh w, w = (u - 1)/(u + 1), |w| < 0.18, ten series
-// terms; 45 instructions against the library's 98, error <= 1.5 ulp
+// terms; 45 instructions against the library's 98. Error 1.93 ulp on the host, <= 2.43 with the device's 1-ulp division ("<= 1.5" stood
+// here). DOMAIN [0.65, 1.5] (12 ulp off at 0.6 already); the one caller stays within [0.6997, 1.03]: h0 <= 11 km, T_sl saturated to
+// 288.15 +- 50 K by the host, h >= H_MIN (tests/test_math_primitives_host.py pins that range).
 FB_KC(KC_LN_C3, 2.0 / 3); FB_KC(KC_LN_C5, 2.0 / 5); FB_KC(KC_LN_C7, 2.0 / 7); FB_KC(KC_LN_C9, 2.0 / 9); FB_KC(KC_LN_C11, 2.0 / 11);
 FB_KC(KC_LN_C13, 2.0 / 13); FB_KC(KC_LN_C15, 2.0 / 15); FB_KC(KC_LN_C17, 2.0 / 17); FB_KC(KC_LN_C19, 2.0 / 19); FB_KC(KC_LN_C21, 2.0 / 21);
 template <class KP = KLit>
@@ -267,7 +290,7 @@ FBD double log_near1(double u, const KP& K = KP{}) {
 // evaluation, ~1 200 instructions, made NED 35 % slower than ECEF): k = round(x 2/pi), r = x - k pi/2 by a three-constant
 // Cody-Waite reduction carried by fma (exact to 1e-17 for |k| < 2^20), Taylor polynomials of sin r / cos r on |r| <= pi/4 to r^17 / r^16
 // (truncation < 1e-17), quadrant by k mod 4. ~40 instructions, <= 1.5 ulp for |x| < 1e6 rad (a heading state that winds up through
-// 160 000 full turns), degrading by one ulp per further factor of two; NaN and inf give NaN like the library.
+// 160 000 full turns; measured 1.48 ulp on the host), degrading by one ulp per further factor of two; NaN and inf give NaN like the library.
 FBD void sincos_step(double x, double& s, double& c) {
     const double k = __builtin_rint(x * 0.6366197723675814);
     double r = __builtin_fma(-k, 1.5707963267948966, x);
@@ -514,7 +537,7 @@ FBD void isa_data(real h, real T_sl, real p_sl, real& T, real& p, real& lnp, int
     lnp = kc<KC_ISA_LNP>(K) * ln_u0;
     if constexpr (FAST && sizeof(real) == 8) {
         // p / p_sl = u0^c, c = g / (beta R) = 5.2559: u0^5 by multiplication, u0^(c - 5) = exp(y) with |y| = 0.256 |ln u0| < 0.1 straight from
-        // the series (no range reduction, degree 9: 3e-17) — 15 arithmetic instructions instead of the library exp's ~40
+        // the series (no range reduction, degree 9: the truncation is 2.8e-17 at |y| = 0.1, measured by tests/test_math_primitives_host.py) — 15 arithmetic instructions instead of the library exp's ~40
         constexpr real cfrac = KC<KC_ISA_CFRAC>::v;
         static_assert(cfrac == -isa::g_std / (beta[0] * isa::R) - 5 && cfrac > FBL(0.25) && cfrac < FBL(0.26), "the exponent of the troposphere's pressure law");
         const real y = kc<KC_ISA_CFRAC>(K) * ln_u0;

@@ -240,6 +240,7 @@ static int32_t copy_rows(fb_handle h, double* dev, const double* host_in, double
 #include "fb_dfreq.inc"
 #include "fb_dpid.inc"
 #include "fb_dtracker.inc"
+#include "fb_mathprobe.inc"
 struct ncclUniqueIdBlob { char internal[128]; };   // ncclUniqueId (rccl.h:40-43), passed by value
 
 // The scratch rows of the stepping kernels (ctl_bak, duo_pld, duo_tap) are zeroed when a handle is created: hipMalloc hands out zero pages in

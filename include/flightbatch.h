@@ -885,6 +885,38 @@ int32_t fb_timing_end(fb_handle h, float* ms, int64_t* n_launches);
 int32_t fb_timing_begin_per_launch(fb_handle h, int64_t max_launches);
 int32_t fb_timing_launches(fb_handle h, float* ms, int64_t cap, int64_t* n);
 
+/* The device math primitives of the stepping kernels, one call per element: the verb behind tests/test_gpu_math_primitives.py, which holds
+ * each primitive to a long double reference in ulps (docs/design/k_step_air.md, "Math primitives, measured"). No handle: one kernel on the
+ * CURRENT device's null stream, complete on return. a, b, out0, out1 are host arrays of n doubles; b may be NULL for a one-argument op and
+ * out1 for a one-output op. The fp32 ops (FB_MP_F32_*) convert a, b to float on the device (pass values that are floats already) and return
+ * their float results widened, which is exact.
+ *   op                              a, b        out0, out1
+ *   FB_MP_SQRT, FB_MP_RSQRT         x           sqrt x / 1 / sqrt x            (the hand-written fp64 forms)
+ *   FB_MP_DIV                       a, b        a / b                          (fp64 division as the build's flags compile it)
+ *   FB_MP_RCP                       x           1 / x
+ *   FB_MP_HALF_ANGLE                y, x        cos, sin of atan2(y, x) / 2
+ *   FB_MP_ATAN2_TAB(_XPOS)          y, x        atan2_tab<false> / <true>
+ *   FB_MP_LOG_NEAR1                 u           log u
+ *   FB_MP_SINCOS_STEP               x           sin x, cos x
+ *   FB_MP_ISA_FAST, FB_MP_ISA       h, T_sl     out0 [3 x n]: T, p / p_sl, log(p / p_sl); out1: the status bits (FB_ST_ISA_RANGE) as a double
+ *   FB_MP_ATAN_TABLE                k           entry min(max((int)k, 0), 32) of atan2_tab's staged table atan(k / 32)
+ *   FB_MP_LIB_EXP, _LOG             x           the library's exp / log as the hot path compiles them
+ *   FB_MP_LIB_SINCOS                x           the library's sin x, cos x
+ *   FB_MP_LIB_ATAN2                 y, x        the library's atan2
+ *   FB_MP_F32_ATAN2_FAST(_XPOS)     y, x        atan2_fast<false> / <true>
+ *   FB_MP_F32_EXP_STEP, _LOG_STEP   x           exp x / log x through the base-2 hardware functions
+ *   FB_MP_F32_SQRT, _RSQRT          x           sqrtf, rsqrtf
+ *   FB_MP_F32_DIV                   a, b        a / b in fp32
+ * Refused, with nothing launched: an op outside the two ranges, n outside 1 .. FB_MP_N_MAX, a NULL a or out0, a NULL b or out1 where the op
+ * needs it. */
+enum { FB_MP_SQRT = 0, FB_MP_RSQRT, FB_MP_DIV, FB_MP_RCP, FB_MP_HALF_ANGLE, FB_MP_ATAN2_TAB, FB_MP_ATAN2_TAB_XPOS, FB_MP_LOG_NEAR1,
+       FB_MP_SINCOS_STEP, FB_MP_ISA_FAST, FB_MP_ISA, FB_MP_ATAN_TABLE, FB_MP_LIB_EXP, FB_MP_LIB_LOG, FB_MP_LIB_SINCOS, FB_MP_LIB_ATAN2,
+       FB_MP_F64_END,
+       FB_MP_F32_ATAN2_FAST = 32, FB_MP_F32_ATAN2_FAST_XPOS, FB_MP_F32_EXP_STEP, FB_MP_F32_LOG_STEP, FB_MP_F32_SQRT, FB_MP_F32_RSQRT,
+       FB_MP_F32_DIV, FB_MP_F32_END,
+       FB_MP_N_MAX = 1 << 24 };
+int32_t fb_math_probe(int32_t op, int64_t n, const double* a, const double* b, double* out0, double* out1);
+
 const char* fb_last_error(void);
 const char* fb_version(void);
 
