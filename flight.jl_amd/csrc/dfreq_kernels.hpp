@@ -19,7 +19,7 @@
 // pm and smin = sqrt (fb_dfreq.inc).
 // Lanes past the batch's end work on the last system (pair) and store nothing, so a wave never diverges on the batch size.
 #pragma once
-#include "lss_group.hpp"
+#include "freq_group.hpp"   // mag2, closer_to_one
 #include "../../include/flightbatch.h"
 
 namespace fbw {
@@ -57,15 +57,6 @@ struct DMarginArgs {
     int64_t n;
     int nx, nu, ny, G, iu, iy, nw;
 };
-
-__device__ __forceinline__ double mag2(double lr, double li) { return fma(lr, lr, li * li); }
-// whether the gain margin g = -Re L* is closer to 1 than h is, in either direction: max(g, 1 / g) < max(h, 1 / h) without dividing
-__device__ __forceinline__ bool closer_to_one(double g, double h) {
-    if (g >= 1.0 && h >= 1.0) return g < h;
-    if (g < 1.0 && h < 1.0) return g > h;
-    const double gh = g * h;
-    return g >= 1.0 ? gh < 1.0 : gh > 1.0;
-}
 
 // c inv(z I - Phi) gamma + d at z = (cz, sz) for the system whose row r of [-Phi | gamma] this lane holds (np, g0), c in the group's cv, by
 // the whole group: Gauss-Jordan with the family's pivot rule on |z|^2, the scaled pivot row through the group's panel, every step a

@@ -5,8 +5,8 @@
 // freqresp, margin, poles and damp on a discrete system are what these verbs compute for a batch.
 // Every refusal is decided here, before anything is launched. The host forms theta_k = w_k Ts and its cosine and sine with the C library
 // (the device library is built with -fapprox-func: no trigonometric function is evaluated on the device), and turns the point z* of a
-// crossing back into w* = atan2(Im z*, Re z*) / Ts. The grid response runs in slices of whole frequencies, as fb_lss_margins' stage 1 does
-// (fb_margins.inc: MARGINS_WG_MAX one-wave workgroups per launch).
+// crossing back into w* = atan2(Im z*, Re z*) / Ts. The grid check (with Ts: the Nyquist refusal, cos and sin), the sliced grid response and
+// the margins' finishing step are the ones the continuous verbs use (fb_pid.inc).
 
 // what the three d verbs ask of their handle: a LinearizedSS handle with a model that is sampled
 static int32_t dverb_handle(const char* verb, fb_handle h, int nx_max, const char* limit) {
@@ -14,51 +14,6 @@ static int32_t dverb_handle(const char* verb, fb_handle h, int nx_max, const cha
     if (int32_t rc = verb_handle(verb, h, nx_max, "call", limit)) return rc;
     if (int32_t rc = verb_model(verb, h)) return rc;
     if (!(h->lss->Ts > 0.0)) return fail("%s: a discrete-time verb on a continuous model: sample it first (fb_lss_c2d, or fb_lss_set_sampled on a model that holds Phi and Gamma)", verb);
-    return 0;
-}
-
-// the channel and the grid of fb_lss_dfreqresp and fb_lss_dmargins; cs, sn: cos and sin of theta_k = w_k Ts. `increasing`: the margins' grid
-static int32_t dfreq_check_grid(const char* verb, fb_handle h, int32_t iu, int32_t iy, const double* w, int32_t nw, int nw_min, bool increasing,
-                                std::vector<double>& cs, std::vector<double>& sn) {
-    const LssState* L = h->lss;
-    const double pi = 3.14159265358979323846;
-    if (iu < 0 || iu >= L->nu) return fail("%s: iu = %d is outside [0, %d)", verb, (int)iu, L->nu);
-    if (iy < 0 || iy >= L->ny) return fail("%s: iy = %d is outside [0, %d)", verb, (int)iy, L->ny);
-    if (!w) return fail("%s: the frequency grid w is required", verb);
-    if (nw < nw_min || nw > 1024) return fail("%s: nw = %d, the grid takes %d <= nw <= 1024 frequencies", verb, (int)nw, nw_min);
-    cs.resize(nw); sn.resize(nw);
-    double before = 0.0;
-    for (int k = 0; k < nw; k++) {
-        if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail("%s: w[%d] = %g, every frequency must be positive and finite", verb, k, w[k]);
-        const double th = w[k] * L->Ts;
-        if (!(th <= pi)) return fail("%s: w[%d] = %.17g is above the Nyquist frequency pi/Ts = %.17g (Ts = %g)", verb, k, w[k], pi / L->Ts, L->Ts);
-        if (increasing && k > 0 && !(th > before))
-            return fail("%s: w[%d] = %g after w[%d] = %g, the grid's angles w Ts must strictly increase", verb, k, w[k], k - 1, w[k - 1]);
-        before = th;
-        cs[k] = std::cos(th); sn[k] = std::sin(th);
-    }
-    return 0;
-}
-
-// frequencies per launch of the grid response, 0 (refused) when one frequency of the batch does not fit a launch
-static int32_t dfreq_slice(const char* verb, fb_handle h, int64_t* slice) {
-    const int ng = fbg::WAVE / group_for(h->lss->nx);
-    *slice = MARGINS_WG_MAX * ng / h->n;
-    if (*slice < 1) return fail("%s: %lld systems exceed the %lld one launch of the grid response takes at nx = %d", verb, (long long)h->n,
-                                (long long)(MARGINS_WG_MAX * ng), h->lss->nx);
-    return 0;
-}
-
-// k_lss_dfreqresp of channel (iu, iy) on the grid d_cs, d_sn [nw] (device) into re, im [nw x n] (device), `slice` frequencies to a launch
-static int32_t dfreq_grid(fb_handle h, int32_t iu, int32_t iy, const double* d_cs, const double* d_sn, int32_t nw, int64_t slice, double* re, double* im) {
-    const int64_t n = h->n;
-    for (int64_t k0 = 0; k0 < nw; k0 += slice) {
-        fbw::DFreqArgs a = {};
-        verb_args(a, h);
-        a.cs = d_cs + k0; a.sn = d_sn + k0; a.re = re + k0 * n; a.im = im + k0 * n;
-        a.iu = iu; a.iy = iy; a.nw = (int)std::min<int64_t>(slice, nw - k0);
-        if (int32_t rc = family_launch(h, group_for(a.nx), a.n * a.nw, a, [](auto P) { return fbw::k_lss_dfreqresp<P.value>; })) return rc;
-    }
     return 0;
 }
 
@@ -81,10 +36,10 @@ int32_t fb_lss_dfreqresp(fb_handle h, int32_t iu, int32_t iy, const double* w, i
     static const char* verb = "fb_lss_dfreqresp";
     if (int32_t rc = dverb_handle(verb, h, FB_MARGINS_NX_MAX, "FB_MARGINS_NX_MAX")) return rc;
     std::vector<double> cs, sn;
-    if (int32_t rc = dfreq_check_grid(verb, h, iu, iy, w, nw, 1, false, cs, sn)) return rc;
+    if (int32_t rc = freq_check_grid(verb, h, iu, iy, w, nw, 1, false, h->lss->Ts, &cs, &sn)) return rc;
     if (!re || !im) return fail("%s: re and im are required", verb);
     int64_t slice = 0;
-    if (int32_t rc = dfreq_slice(verb, h, &slice)) return rc;
+    if (int32_t rc = freq_slice(verb, h, &slice)) return rc;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->n, np = n * (size_t)nw;
     DevBlocks blocks;
@@ -93,7 +48,7 @@ int32_t fb_lss_dfreqresp(fb_handle h, int32_t iu, int32_t iy, const double* w, i
     double *d_re = d + 2 * nw, *d_im = d_re + np;
     HIPCHK(hipMemcpyAsync(d, cs.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d + nw, sn.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
-    if (int32_t rc = dfreq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
+    if (int32_t rc = freq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
     HIPCHK(hipMemcpyAsync(re, d_re, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(im, d_im, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -105,12 +60,11 @@ int32_t fb_lss_dmargins(fb_handle h, int32_t iu, int32_t iy, const double* w, in
     static const char* verb = "fb_lss_dmargins";
     if (int32_t rc = dverb_handle(verb, h, FB_MARGINS_NX_MAX, "FB_MARGINS_NX_MAX")) return rc;
     std::vector<double> cs, sn;
-    if (int32_t rc = dfreq_check_grid(verb, h, iu, iy, w, nw, 2, true, cs, sn)) return rc;
+    if (int32_t rc = freq_check_grid(verb, h, iu, iy, w, nw, 2, true, h->lss->Ts, &cs, &sn)) return rc;
     if (!sel || !counts || !status) return fail("%s: sel, counts and status are required", verb);
-    if (h->n * (int64_t)nw > ((int64_t)1 << 31) - 1)
-        return fail("%s: %lld systems x %d frequencies exceed the 2^31 - 1 pairs of one launch grid", verb, (long long)h->n, (int)nw);
+    if (int32_t rc = freq_check_pairs(verb, h, nw)) return rc;
     int64_t slice = 0;
-    if (int32_t rc = dfreq_slice(verb, h, &slice)) return rc;
+    if (int32_t rc = freq_slice(verb, h, &slice)) return rc;
 
     HIPCHK(hipSetDevice(h->device));
     const double Ts = h->lss->Ts;
@@ -125,7 +79,7 @@ int32_t fb_lss_dmargins(fb_handle h, int32_t iu, int32_t iy, const double* w, in
     HIPCHK(hipMemcpyAsync(d, cs.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d + nw, sn.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
     if (gain) HIPCHK(hipMemcpyAsync(d_gain, gain, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    if (int32_t rc = dfreq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
+    if (int32_t rc = freq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
     fbw::DMarginArgs a = {};
     verb_args(a, h);
     a.cs = d; a.sn = d + nw; a.re = d_re; a.im = d_im; a.gain = gain ? d_gain : nullptr;
@@ -138,17 +92,14 @@ int32_t fb_lss_dmargins(fb_handle h, int32_t iu, int32_t iy, const double* w, in
     HIPCHK(hipMemcpyAsync(counts, di, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(status, di + 2 * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    // w* from the point of the circle, gm, pm and smin from what the kernel selected: the host's atan2, division and sqrt
-    const double inf = HUGE_VAL, nan = std::nan(""), deg = 180.0 / 3.14159265358979323846;
+    // w* from the point of the circle (the host's atan2) around the finishing step, and the grid frequency of smin from its index
+    const double nan = std::nan("");
     for (size_t i = 0; i < n; i++) {
-        if (status[i] & (FB_MARGINS_NOT_FINITE | FB_MARGINS_SINGULAR)) continue;   // (the kernel stored NaN in every row)
         const double wpc = counts[i] ? std::atan2(sel[i], sel[n + i]) / Ts : nan;
         const double wgc = counts[n + i] ? std::atan2(sel[2 * n + i], sel[3 * n + i]) / Ts : nan;
-        sel[i] = counts[i] ? -1.0 / sel[4 * n + i] : inf;
+        if (!margins_finish(sel, counts, status, n, i)) continue;
         sel[n + i] = wpc;
-        sel[2 * n + i] = counts[n + i] ? std::atan2(-sel[7 * n + i], -sel[6 * n + i]) * deg : inf;
         sel[3 * n + i] = wgc;
-        sel[8 * n + i] = std::sqrt(sel[8 * n + i]);
         const double ks = sel[9 * n + i];
         sel[9 * n + i] = ks >= 0.0 && ks < (double)nw ? w[(int)ks] : nan;
     }

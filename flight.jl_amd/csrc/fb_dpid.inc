@@ -1,6 +1,6 @@
 // fb_dpid.inc — the metrics of optimize_PID on a SAMPLED Model(lss) batch under the sampled PID law (include/flightbatch.h:
 // fb_lss_dpid_metrics; kernels: dpid_kernels.hpp, and fbw::k_lss_dfreqresp for P(z) on the grid; docs/design/linearize.md, "Discrete PID
-// design on the device"). Included by fb_capi.hip after fb_dfreq.inc (the d verbs' handle and grid checks, the sliced grid response).
+// design on the device"). Included by fb_capi.hip after fb_dfreq.inc (the d verbs' handle check; the grid check and the sliced grid response are fb_pid.inc's).
 // Reference: f_periodic! of PID, FP/control.jl:431-471, is the law Cessna172Xv2 and Robot2D run every dt = 0.02; FA design/pidopt.jl designs
 // its gains on the continuous compensator (fb_pid.inc). Here one call evaluates pidopt.jl's metrics of every (system, candidate) pair under
 // the law as it runs; the search that proposes the candidates is host-side (flightbatch/dpid.py).
@@ -13,7 +13,7 @@ int32_t fb_lss_dpid_metrics(fb_handle h, int32_t iu, int32_t iy, const double* w
     static const char* verb = "fb_lss_dpid_metrics";
     if (int32_t rc = dverb_handle(verb, h, FB_DPID_NX_MAX, "FB_DPID_NX_MAX")) return rc;
     std::vector<double> cs, sn;
-    if (int32_t rc = dfreq_check_grid(verb, h, iu, iy, w, nw, 1, false, cs, sn)) return rc;
+    if (int32_t rc = freq_check_grid(verb, h, iu, iy, w, nw, 1, false, h->lss->Ts, &cs, &sn)) return rc;
     if (m < 1 || m > 64) return fail("%s: m = %d, a call takes 1 <= m <= 64 candidates per system", verb, (int)m);
     if (h->n * (int64_t)m > ((int64_t)1 << 31) - 1)
         return fail("%s: %lld systems x %d candidates exceed the 2^31 - 1 pairs of one launch grid", verb, (long long)h->n, (int)m);
@@ -44,7 +44,7 @@ int32_t fb_lss_dpid_metrics(fb_handle h, int32_t iu, int32_t iy, const double* w
                         verb, lo, hi, (long long)(k % n), (long long)(k / n));
     }
     int64_t slice = 0;
-    if (int32_t rc = dfreq_slice(verb, h, &slice)) return rc;
+    if (int32_t rc = freq_slice(verb, h, &slice)) return rc;
     HIPCHK(hipSetDevice(h->device));
     // one device block: cos | sin | P(z) re | im | pid | bounds | metrics | cost; counts | status apart
     const size_t nb = bounds ? 2 * nc : 0, nm = metrics ? 5 * nc : 0, nk = counts ? 2 * nc : 0;
@@ -58,7 +58,7 @@ int32_t fb_lss_dpid_metrics(fb_handle h, int32_t iu, int32_t iy, const double* w
     HIPCHK(hipMemcpyAsync(d + nw, sn.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d_pid, pid, sizeof(double) * 4 * nc, hipMemcpyHostToDevice, h->stream));
     if (bounds) HIPCHK(hipMemcpyAsync(d_bnd, bounds, sizeof(double) * nb, hipMemcpyHostToDevice, h->stream));
-    if (int32_t rc = dfreq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
+    if (int32_t rc = freq_grid(h, iu, iy, d, d + nw, nw, slice, d_re, d_im)) return rc;
     verb_args(a, h);
     a.cs = d; a.sn = d + nw; a.pre = d_re; a.pim = d_im; a.pid = d_pid; a.bounds = bounds ? d_bnd : nullptr;
     a.metrics = metrics ? d_met : nullptr; a.cost = d_cost; a.counts = counts ? di : nullptr; a.status = di + nk;

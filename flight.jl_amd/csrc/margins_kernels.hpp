@@ -15,7 +15,7 @@
 // of products, no division and no transcendental: gm, pm and smin = sqrt are the host's (fb_margins.inc).
 // Lanes past the batch's end work on the last system and store nothing, so a wave never diverges on the batch size.
 #pragma once
-#include "lss_group.hpp"
+#include "freq_group.hpp"   // mag2, closer_to_one
 #include "../../include/flightbatch.h"
 
 namespace fbn {
@@ -37,15 +37,6 @@ struct MarginArgs {
     int64_t n;
     int nx, nu, ny, G, iu, iy, nw;
 };
-
-__device__ __forceinline__ double mag2(double lr, double li) { return fma(lr, lr, li * li); }
-// whether the gain margin g = -Re L* is closer to 1 than h is, in either direction: max(g, 1 / g) < max(h, 1 / h) without dividing
-__device__ __forceinline__ bool closer_to_one(double g, double h) {
-    if (g >= 1.0 && h >= 1.0) return g < h;
-    if (g < 1.0 && h < 1.0) return g > h;
-    const double gh = g * h;
-    return g >= 1.0 ? gh < 1.0 : gh > 1.0;
-}
 
 template <int P>
 __global__ __launch_bounds__(WAVE) void k_lss_margins(MarginArgs a) {

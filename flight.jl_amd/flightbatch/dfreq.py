@@ -20,7 +20,7 @@ import numpy as np
 
 from ._lib import FlightBatchError, check, lib
 from .lss import LinearWorld
-from .margins import KMAX, NW_MAX, MarginsResult
+from .margins import NW_MAX, MarginsResult, _margins_call
 from .modeling import _pd, _pi
 from .pidopt import _channel
 from .poles import _g3
@@ -71,22 +71,7 @@ def dmargins(world, u=0, y=0, w=None, gain=None, all=False) -> MarginsResult:
     rad/s (default default_dgrid(world.Ts)); gain: None (ones), a number for the batch or [N]; all=True also returns every kept crossing."""
     _sampled(world, "dmargins")
     iu, iy = _channel(world, u, y)
-    w = _dgrid(world, w, "dmargins", 2)
-    n = world.n
-    if gain is not None:
-        gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64), (n,)))
-    sel, counts, status = np.empty((10, n)), np.empty((2, n), dtype=np.int32), np.empty(n, dtype=np.int32)
-    every = np.empty((6, KMAX, n)) if all else None
-    check(lib.fb_lss_dmargins(world._h, iu, iy, _pd(w), w.size, None if gain is None else _pd(gain), _pd(sel), _pi(counts),
-                              None if every is None else _pd(every), _pi(status)))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        res = MarginsResult(gm=sel[0].copy(), wpc=sel[1].copy(), pm=sel[2].copy(), wgc=sel[3].copy(), ms=1.0 / sel[8], wms=sel[9].copy(),
-                            npc=counts[0].copy(), ngc=counts[1].copy(), status=status, l_pc=sel[4] + 1j * sel[5], l_gc=sel[6] + 1j * sel[7])
-        if every is not None:
-            res.wpc_all, res.wgc_all = every[0].T.copy(), every[3].T.copy()
-            res.gm_all = (-1.0 / every[1]).T.copy()
-            res.pm_all = np.degrees(np.arctan2(-every[5], -every[4])).T.copy()
-    return res
+    return _margins_call(lib.fb_lss_dmargins, world, iu, iy, _dgrid(world, w, "dmargins", 2), gain, all)
 
 
 @dataclass

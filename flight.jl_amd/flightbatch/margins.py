@@ -69,20 +69,16 @@ def _margin_grid(w) -> np.ndarray:
     return w
 
 
-def margins(world, u=0, y=0, w=None, gain=None, all=False) -> MarginsResult:
-    """gain and phase margins of L = gain · P[y, u] of every system of a continuous LinearWorld. u, y: indices or labels; w: the grid in
-    rad/s (default pidopt.default_grid()); gain: None (ones), a number for the batch or [N]; all=True also returns every kept crossing."""
-    if not isinstance(world, LinearWorld):
-        raise FlightBatchError("margins: the world is not a LinearizedSS handle (FB_MODEL_LSS): give it a LinearWorld")
-    iu, iy = _channel(world, u, y)
-    w = _margin_grid(w)
+def _margins_call(fn, world, iu, iy, w, gain, all) -> MarginsResult:
+    """what margins and dmargins share once the world, the channel and the grid are checked: the gain for the batch, the output buffers,
+    the call of fn (fb_lss_margins or fb_lss_dmargins: one signature) and the result"""
     n = world.n
     if gain is not None:
         gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64), (n,)))
     sel, counts, status = np.empty((10, n)), np.empty((2, n), dtype=np.int32), np.empty(n, dtype=np.int32)
     every = np.empty((6, KMAX, n)) if all else None
-    check(lib.fb_lss_margins(world._h, iu, iy, _pd(w), w.size, None if gain is None else _pd(gain), _pd(sel), _pi(counts),
-                             None if every is None else _pd(every), _pi(status)))
+    check(fn(world._h, iu, iy, _pd(w), w.size, None if gain is None else _pd(gain), _pd(sel), _pi(counts),
+             None if every is None else _pd(every), _pi(status)))
     with np.errstate(divide="ignore", invalid="ignore"):
         res = MarginsResult(gm=sel[0].copy(), wpc=sel[1].copy(), pm=sel[2].copy(), wgc=sel[3].copy(), ms=1.0 / sel[8], wms=sel[9].copy(),
                             npc=counts[0].copy(), ngc=counts[1].copy(), status=status, l_pc=sel[4] + 1j * sel[5], l_gc=sel[6] + 1j * sel[7])
@@ -91,3 +87,12 @@ def margins(world, u=0, y=0, w=None, gain=None, all=False) -> MarginsResult:
             res.gm_all = (-1.0 / every[1]).T.copy()
             res.pm_all = np.degrees(np.arctan2(-every[5], -every[4])).T.copy()
     return res
+
+
+def margins(world, u=0, y=0, w=None, gain=None, all=False) -> MarginsResult:
+    """gain and phase margins of L = gain · P[y, u] of every system of a continuous LinearWorld. u, y: indices or labels; w: the grid in
+    rad/s (default pidopt.default_grid()); gain: None (ones), a number for the batch or [N]; all=True also returns every kept crossing."""
+    if not isinstance(world, LinearWorld):
+        raise FlightBatchError("margins: the world is not a LinearizedSS handle (FB_MODEL_LSS): give it a LinearWorld")
+    iu, iy = _channel(world, u, y)
+    return _margins_call(lib.fb_lss_margins, world, iu, iy, _margin_grid(w), gain, all)

@@ -245,3 +245,6 @@ def test_the_six_kernel_instances_are_in_the_library(fb, tmp_path_factory):
         for name in (f"fbp::k_lss_freqresp<{P}>", f"fbp::k_pid_metrics<{P}>"):
             assert name in kernels, sorted(k for k in kernels if k.startswith("fbp::"))
             assert kernels[name]["scratch"] == 0 and kernels[name]["lds"] <= 160 * 1024 and "k_step_" not in name
+        # the grid response works in fbq::Group's panels (csrc/lqr_kernels.hpp): per group of P lanes a P x (P + 1) panel and two side
+        # panels of 8 x P / 2 doubles; 64 / P groups to a workgroup (the sampled twin keeps 5 P + 2 doubles: tests/test_dmargins_host.py)
+        assert kernels[f"fbp::k_lss_freqresp<{P}>"]["lds"] == (P * (P + 1) + 2 * 8 * (P // 2)) * (64 // P) * 8
